@@ -354,6 +354,31 @@ def degree2_pcg_rate(n=128, levels=5):
             "compliance": float((f * u).sum())}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 1 << 20        # node rows kept of a larger Ku: 1 Mi rows x 3 x fp64 = 24 MiB, plus their indices (8 MiB)
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: write what the timed path returned in its last step, Ku (numNodes x 3, fp64), as <path>/Ku.npy.  A Ku
+    above DUMP_LIMIT_BYTES is reduced to a fixed sample of node rows (seed 88, sorted, without repetition) written as
+    Ku_sample.npy, and the sampled node indices as Ku_sample_rows.npy (fp64, exact below 2^53); the sample depends only on
+    the grid, so runs with the same arguments compare row for row."""
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    if out.numel() * out.element_size() <= DUMP_LIMIT_BYTES:
+        written["Ku"] = out.detach().cpu().numpy().astype(np.float64)
+    else:
+        n = out.shape[0]
+        rows = np.sort(np.random.default_rng(88).choice(n, size=min(n, DUMP_SAMPLE_ROWS), replace=False))
+        idx = torch.from_numpy(rows).to(out.device)
+        written["Ku_sample"] = out.index_select(0, idx).cpu().numpy().astype(np.float64)
+        written["Ku_sample_rows"] = rows.astype(np.float64)
+    assert sum(a.nbytes for a in written.values()) <= DUMP_LIMIT_BYTES
+    for name, a in written.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in written.items()}
+
+
 def _rank_main(rank, world, port, argv):
     """entry of a rank process started by `launch_ranks` (fresh interpreter, nothing has touched the GPU yet)"""
     os.environ.update({"RANK": str(rank), "LOCAL_RANK": str(rank), "WORLD_SIZE": str(world), "MASTER_ADDR": "127.0.0.1",
@@ -391,7 +416,15 @@ def main():
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline")
     ap.add_argument("--rank-proxy", type=int, default=0, metavar="N",
                     help="also time one rank's slab of an N-rank CG-MG run on this GPU (tools/rank_proxy.py): an upper bound on strong scaling")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's Ku (or a fixed sample of its rows, at most 64 MB) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs is implemented for --gpus 1 only")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -436,6 +469,7 @@ def main():
     wall = time.perf_counter() - t0
     ms_per_step = wall / args.steps * 1e3
     nvox = ne[0] * ne[1] * ne[2]
+    dumped = dump_outputs(out, args.dump_outputs) if args.dump_outputs else None
 
     kernel_s = time_apply(tps, u, args.steps, 1)
     ab = algorithmic_bytes(ne)
@@ -464,6 +498,8 @@ def main():
                    "grid": list(ne), "parallelism": "1 GPU"},
         "roofline": roofline,
     }
+    if dumped is not None:
+        result["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if not args.no_cg:
         del u, tps
         torch.cuda.empty_cache()

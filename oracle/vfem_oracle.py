@@ -16,10 +16,13 @@ be compiled here (Eigen/TBB/CHOLMOD/Boost are not vendored), so there
 Every function cites the reference lines it follows (paths relative to the reference
 checkout; TPS = VoxelFEM/TensorProductSimulator.hh, MG = VoxelFEM/MultigridSolver.hh).
 """
+import atexit
 import ctypes
 import json
 import os
+import shutil
 import subprocess
+import tempfile
 
 import numpy as np
 
@@ -30,14 +33,17 @@ _LIB = None
 def build_lib(force=False, native=False):
     """Compile voxel_ref.c -> oracle/_build/libvoxel_ref.so (gcc -O2, OpenMP): the checker the tests use.
     native=True: a second copy with the reference's own optimisation flags (VoxelFEM/CMakeLists.txt:43: -O3 -march=native
-    -ffast-math ...), always rebuilt on the host it will run on -- only bench.py's cpu_baseline leg times that one."""
+    -ffast-math ...), always rebuilt on the host it will run on -- only bench.py's cpu_baseline leg times that one.  It goes to a
+    private temporary directory, removed at exit: the bench may run from a tree it cannot write."""
     out_dir = os.path.join(_HERE, "_build")
     src = os.path.join(_HERE, "voxel_ref.c")
-    os.makedirs(out_dir, exist_ok=True)
     if native:
-        so = os.path.join(out_dir, "libvoxel_ref_native.so")
+        tmp = tempfile.mkdtemp(prefix="voxel_ref_native_")
+        atexit.register(shutil.rmtree, tmp, True)
+        so = os.path.join(tmp, "libvoxel_ref_native.so")
         subprocess.check_call(["gcc", "-O3", "-march=native", "-ffast-math", "-funroll-loops", "-fopenmp", "-fPIC", "-shared", "-o", so, src, "-lm"])
         return so
+    os.makedirs(out_dir, exist_ok=True)
     so = os.path.join(out_dir, "libvoxel_ref.so")
     if force or not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
         subprocess.check_call(["gcc", "-O2", "-fopenmp", "-fPIC", "-shared", "-o", so, src, "-lm"])

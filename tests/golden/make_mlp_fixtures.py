@@ -1,5 +1,5 @@
-"""Generates tests/golden/mlp_*.npz by importing the reference's networks.MLP (CPU torch) in this container.
-Run once from the repo root:  python tests/golden/make_mlp_fixtures.py
+"""Generates tests/golden/mlp_*.npz by importing the reference's networks.MLP (CPU torch) from a checkout of the reference.
+Run once from the repo root:  NDR_REFERENCE=<reference checkout> python tests/golden/make_mlp_fixtures.py
 Only inputs and outputs (weights, B, coordinates, densities) are stored; no reference source travels."""
 import os
 import sys
@@ -7,7 +7,9 @@ import sys
 import numpy as np
 import torch
 
-sys.path.insert(0, "/root/reference")
+if not os.environ.get("NDR_REFERENCE"):
+    raise SystemExit("set NDR_REFERENCE to a checkout of the reference (the directory holding networks.py)")
+sys.path.insert(0, os.environ["NDR_REFERENCE"])
 import networks  # noqa: E402  (reference module)
 
 HERE = os.path.dirname(os.path.abspath(__file__))

@@ -2,8 +2,8 @@
 # HBM-side read / write volume of the kernels matching a name: two rocprofv3 counter passes (FETCH_SIZE, WRITE_SIZE) of one command.
 #   tools/fetch_size.sh OUTDIR KERNEL_SUBSTRING python3 tools/xyz.py args...        (counter units: KiB; see DESIGN for the gfx950 factor)
 set -o pipefail
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$1; PAT=$2; shift 2
 case $O in /*) ;; *) O=$R/$O;; esac
 mkdir -p $O

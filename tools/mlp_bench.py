@@ -1,4 +1,4 @@
-import sys, json
-sys.path.insert(0, "/root/repo")
+import os, sys, json
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 print(json.dumps(bench.mlp_rate(), indent=1))

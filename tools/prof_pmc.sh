@@ -3,8 +3,8 @@
 #   tools/prof_pmc.sh OUTDIR KERNEL_SUBSTRING python3 tools/xyz.py args...
 # writes OUTDIR/summary.json (per-kernel counter sums, tools/pmc_summary.py) and OUTDIR/kernel_stats.csv
 set -o pipefail
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$1; PAT=$2; shift 2
 case $O in /*) ;; *) O=$R/$O;; esac
 mkdir -p $O
