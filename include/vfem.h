@@ -314,6 +314,17 @@ int vfem_projection_backprop(int64_t n, double beta, const double *g, const doub
 int vfem_oc_candidate(int64_t n, const double *x0, const double *dJ, const double *dc, double lambda, double move, double *out,
                       void *stream);
 int vfem_mean(int64_t n, const double *x, double *mean_host, void *stream);
+/* LangelaarFilter (TopologyOptimizationFilter.hh:164-278; the reference fixes eps = 1e-4, p = 40, q = 40 - 1.58).  The layer
+ * axis is n[2], so 2-D grids [nx][ny] are passed as {nx, 1, ny} (same flat order).  apply writes out and the smax cache
+ * (smax = 1 on layer 0); backprop takes both caches of the apply it differentiates plus `vars`, and returns
+ * grad = lambda dsmin_dx1(vars, smax) with the adjoint march over n[2] layers (the reference's computeLagrangeMultipliers,
+ * :211-226, bounds it by n[1] instead; identical when n[1] == n[2] and in 2-D).  A support whose sum of out^p is 0 (below the
+ * smallest normal double) contributes 0, where the reference computes 0 * inf.  work: caller-provided device scratch of
+ * 2 n[0] n[1] doubles.  Both run ceil(n[2] / 8) kernel launches on `stream`. */
+int vfem_langelaar_apply(const int64_t n_host[3], double eps, double p, double q, const double *in, double *out, double *smax,
+                         void *stream);
+int vfem_langelaar_backprop(const int64_t n_host[3], double eps, double p, double q, const double *g, const double *vars,
+                            const double *out, const double *smax, double *work, double *grad, void *stream);
 
 /* ---- Fourier-feature MLP density field: networks.MLP (networks.py:128-185), out_features = 1 ----
  * n_layers counts Linear layers as the reference does: Linear(2 es, nn), (n_layers - 2) x Linear(nn, nn), Linear(nn, 1).

@@ -1272,6 +1272,26 @@ int vfem_oc_candidate(int64_t n, const double *x0, const double *dJ, const doubl
                       void *stream) {
     VFEM_TRY launch_oc_candidate(n, x0, dJ, dc, lambda, move, out, S(stream)); VFEM_CATCH
 }
+static void check_langelaar(const int64_t n[3], double eps, double p, double q) {
+    for (int d = 0; d < 3; ++d)
+        if (n[d] < 1 || n[d] > (1 << 30)) throw Error("invalid grid dimensions");
+    if (n[0] * n[1] > (int64_t) 1 << 31) throw Error("grid too large");
+    if (!(eps > 0) || !(p > 1) || !(q > 0)) throw Error("LangelaarFilter needs eps > 0, p > 1, q > 0");
+}
+int vfem_langelaar_apply(const int64_t n[3], double eps, double p, double q, const double *in, double *out, double *smax,
+                         void *stream) {
+    VFEM_TRY
+    check_langelaar(n, eps, p, q);
+    launch_langelaar_apply((int) n[0], (int) n[1], (int) n[2], eps, p, q, in, out, smax, S(stream));
+    VFEM_CATCH
+}
+int vfem_langelaar_backprop(const int64_t n[3], double eps, double p, double q, const double *g, const double *vars,
+                            const double *out, const double *smax, double *work, double *grad, void *stream) {
+    VFEM_TRY
+    check_langelaar(n, eps, p, q);
+    launch_langelaar_backprop((int) n[0], (int) n[1], (int) n[2], eps, p, q, g, vars, out, smax, work, grad, S(stream));
+    VFEM_CATCH
+}
 int vfem_mean(int64_t n, const double *x, double *mean_host, void *stream) {
     VFEM_TRY
     DevBuf<double> tmp; tmp.alloc(2048 + 8);

@@ -196,6 +196,11 @@ void launch_box_filter(int nx, int ny, int nz, int r, const double *in, double *
 void launch_projection(long long n, double beta, const double *x, const double *g, double *out, int mode, hipStream_t s);
 void launch_oc_candidate(long long n, const double *x0, const double *dJ, const double *dc, double lambda, double m, double *out, hipStream_t s);
 void launch_sum(long long n, const double *a, double *scratch, double *out, hipStream_t s);
+// LangelaarFilter marches (kernels_filter.hip); layer axis nz, work: 2 nx ny doubles
+void launch_langelaar_apply(int nx, int ny, int nz, double eps, double p, double q, const double *in, double *out, double *smax,
+                            hipStream_t s);
+void launch_langelaar_backprop(int nx, int ny, int nz, double eps, double p, double q, const double *g, const double *vars,
+                               const double *out, const double *smax, double *work, double *grad, hipStream_t s);
 
 void launch_apply_q2(int nx, int ny, int nz, const double *K0, const double *E, const double *u, double *out, hipStream_t s);
 void launch_apply_q2_pencil(int nx, int ny, int nz, const double *mode_table, const double *E, const double *u, double *out, hipStream_t s);

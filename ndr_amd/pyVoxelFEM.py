@@ -910,10 +910,54 @@ class PythonFilter(_Filter):
 
 
 class LangelaarFilter(_Filter):
-    def apply_dev(self, x):
-        raise RuntimeError("LangelaarFilter is not part of the accelerated path (never used by the drivers)")
+    """Additive-manufacturing overhang filter (TopologyOptimizationFilter.hh:164-278): each element of layer k >= 1 (the
+    last grid axis) is capped by a smooth maximum of the filtered elements that support it on layer k-1, so the forward is
+    a march up the layers and the backward a march down (vfem_langelaar_*).  As in the reference, backprop differentiates
+    the most recent apply: its output and smax caches stay on the device, owned by the filter (the tensor apply_dev returns
+    is that output cache).  The adjoint march covers all layers also on 3-D grids with ny != nz, where the reference's loop
+    stops after ny layers."""
 
-    backprop_dev = apply_dev
+    _EPS, _P, _Q = 1e-4, 40.0, 40.0 - 1.58      # fixed by the reference (:266-276), not exposed by its binding
+
+    def __init__(self):
+        super().__init__()
+        self._out = self._smax = self._work = None
+
+    def _set_grid(self, dims):
+        super()._set_grid(dims)
+        self._out = self._smax = self._work = None
+
+    def _nl(self):
+        g = self._grid
+        return (ctypes.c_int64 * 3)(*((g[0], 1, g[1]) if len(g) == 2 else g))    # layer axis last
+
+    def _check_size(self, *ts):
+        n = int(np.prod(self._grid))
+        for t in ts:
+            if t.numel() != n:
+                raise RuntimeError("LangelaarFilter: input of size %d does not match the grid (%d elements)" % (t.numel(), n))
+
+    def apply_dev(self, x):
+        self._check()
+        self._check_size(x)
+        out, smax = torch.empty_like(x), torch.empty_like(x)
+        _lib.check(_lib.load().vfem_langelaar_apply(self._nl(), self._EPS, self._P, self._Q, _ptr(x), _ptr(out), _ptr(smax),
+                                                    _stream()))
+        self._out, self._smax = out, smax
+        return out
+
+    def backprop_dev(self, g, x):
+        self._check()
+        if self._out is None:
+            raise RuntimeError("LangelaarFilter: backprop called before apply")
+        self._check_size(g, x)
+        n = self._nl()
+        if self._work is None:
+            self._work = torch.empty(2 * n[0] * n[1], dtype=torch.float64, device=_dev())
+        grad = torch.empty_like(g)
+        _lib.check(_lib.load().vfem_langelaar_backprop(n, self._EPS, self._P, self._Q, _ptr(g), _ptr(x), _ptr(self._out),
+                                                       _ptr(self._smax), _ptr(self._work), _ptr(grad), _stream()))
+        return grad
 
 
 def applyFilter(filter, x):
