@@ -307,7 +307,8 @@ int vfem_gmg_pcg(vfem_gmg *mg, double *x, const double *b, int max_iter, double 
 /* ---- design-update path, element-grid arrays [n0][n1][n2] fp64 (2-D grids: n2 = 1) ----
  * SmoothingFilter apply / backprop (TopologyOptimizationFilter.hh:105-162; transpose != 0 => A^T), ProjectionFilter apply /
  * backprop (:55-79), mean for TotalVolumeConstraint (TopologyOptimizationConstraint.hh:21-34), and the OC candidate step
- * clip(x0 sqrt(dJ/(dc lambda)), max(x0-m,0), min(x0+m,1)) of OCOptimizer::step (OptimalityCriterion.hh:47-50). */
+ * clip(x0 sqrt(dJ/(dc lambda)), max(x0-m,0), min(x0+m,1)) of OCOptimizer::step (OptimalityCriterion.hh:47-50); where
+ * dJ/(dc lambda) < 0 the candidate is the lower edge max(x0-m,0) (the reference: NaN).  vfem_mean refuses n < 1. */
 int vfem_box_filter(const int64_t n_host[3], int radius, const double *in, double *out, int transpose, void *stream);
 int vfem_projection(int64_t n, double beta, const double *x, double *out, void *stream);
 int vfem_projection_backprop(int64_t n, double beta, const double *g, const double *vars, double *out, void *stream);

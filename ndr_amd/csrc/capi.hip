@@ -1294,12 +1294,15 @@ int vfem_langelaar_backprop(const int64_t n[3], double eps, double p, double q, 
 }
 int vfem_mean(int64_t n, const double *x, double *mean_host, void *stream) {
     VFEM_TRY
+    // the mean of nothing is undefined (the reference's Eigen mean() gives 0/0 = NaN, which would end the OC bisection on a
+    // meaningless multiplier without a word): refuse it
+    if (n < 1) throw Error("vfem_mean: empty vector");
     DevBuf<double> tmp; tmp.alloc(2048 + 8);
     launch_sum(n, x, tmp.p + 8, tmp.p, S(stream));
     double v = 0.0;
     VFEM_HIP(hipMemcpyAsync(&v, tmp.p, sizeof(double), hipMemcpyDeviceToHost, S(stream)));
     VFEM_HIP(hipStreamSynchronize(S(stream)));
-    *mean_host = n > 0 ? v / (double) n : 0.0;
+    *mean_host = v / (double) n;
     VFEM_CATCH
 }
 

@@ -341,7 +341,8 @@ void launch_projection(long long n, double beta, const double *x, const double *
     VFEM_HIP(hipGetLastError());
 }
 
-// OC candidate: clip(x0 sqrt(dJ / (dc lambda)), max(x0 - m, 0), min(x0 + m, 1))
+// OC candidate: clip(x0 sqrt(dJ / (dc lambda)), max(x0 - m, 0), min(x0 + m, 1)); fmax drops the NaN of a negative ratio, which
+// therefore yields the lower edge of the move window (the reference: NaN)
 __global__ void __launch_bounds__(256) k_oc_candidate(long long n, const double *__restrict__ x0, const double *__restrict__ dJ,
                                                       const double *__restrict__ dc, double lambda, double m, double *__restrict__ out) {
     for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long) gridDim.x * blockDim.x) {
