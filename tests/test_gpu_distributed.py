@@ -152,7 +152,8 @@ def test_distributed_sweeps_overlapped_with_the_halo_exchange(world, ne, levels)
 
 
 @pytest.mark.parametrize("world,ne,levels", [(2, (32, 16, 16), 3), (2, (48, 8, 16), 2),
-                                             (4, (64, 16, 16), 3), (4, (64, 16, 16), 4)])
+                                             (4, (64, 16, 16), 3), (4, (64, 16, 16), 4),
+                                             (2, (32, 8, 264), 3)])       # long rows: level-0 row pairs with nA = 3, level-1 pair rows with nseg = 1
 def test_distributed_pcg_matches_single_process(world, ne, levels):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
