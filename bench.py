@@ -4,13 +4,15 @@
 A "step" is one matrix-free stiffness apply  Ku = K(rho) u  (the SpMV of BASELINE.json's metric) over the
 whole Q1 fp64 voxel grid (default 512^3, `--grid` to change) with u, rho and Ku resident in HBM.  With N > 1
 ranks the grid is split into x-slabs (one per GPU) and every step includes the halo exchange of u
-(`ndr_amd.distributed`); the work is fixed as N grows (strong scaling).  Beside the headline value the same
-JSON line reports
+(`ndr_amd.distributed`); the work is fixed as N grows (strong scaling).  A plain run sets up, warms up, times the
+steps, writes `--dump-outputs` and prints the headline line; nothing else.  With `--full` the same JSON line also
+reports
   * CG-MG iterations/s of the multigrid-preconditioned CG compliance solve (reference settings: tol 1e-4,
     one full-multigrid cycle per iteration, 2+2 symmetric coloured Gauss-Seidel sweeps, zero initial guess),
   * `roofline`: algorithmic HBM bytes of one apply / its measured duration, against the 8 TB/s HBM peak,
   * `cpu_baseline`: the CPU oracle (a port of the reference's element loop with its thread-private
-    accumulators) timed on this host on a bounded sample of the same workload (rank 0, N = 1 only).
+    accumulators) timed on this host on a bounded sample of the same workload (rank 0, N = 1 only),
+  * the 256^3 SpMV, the MLP forward/backward and the degree-2 SpMV and CG-MG rates (N = 1).
 """
 import argparse
 import json
@@ -412,10 +414,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--grid", type=int, nargs=3, default=[512, 512, 512])
-    ap.add_argument("--no-cg", action="store_true", help="skip the CG-MG side measurements")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every side measurement (roofline with launches of its own, other grids, CG-MG, MLP, "
+                         "degree 2, CPU baseline); a plain run does only what the headline needs")
+    ap.add_argument("--no-cg", action="store_true", help="with --full: skip the CG-MG side measurements")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--rank-proxy", type=int, default=0, metavar="N",
-                    help="also time one rank's slab of an N-rank CG-MG run on this GPU (tools/rank_proxy.py): an upper bound on strong scaling")
+                    help="with --full: also time one rank's slab of an N-rank CG-MG run on this GPU (tools/rank_proxy.py): an upper bound on strong scaling")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the last step's Ku (or a fixed sample of its rows, at most 64 MB) as DIR/<name>.npy")
     args = ap.parse_args()
@@ -425,6 +430,8 @@ def main():
         ap.error("--warmup must not be negative")
     if args.dump_outputs and args.gpus > 1:
         ap.error("--dump-outputs is implemented for --gpus 1 only")
+    if args.rank_proxy and not args.full:
+        ap.error("--rank-proxy is a side measurement: give --full as well")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -442,7 +449,7 @@ def main():
 
     if world > 1:
         from ndr_amd import distributed as vd
-        res = vd.bench_apply(ne, args.steps, args.warmup, with_cg=not args.no_cg)
+        res = vd.bench_apply(ne, args.steps, args.warmup, with_cg=args.full and not args.no_cg)
         if rank == 0:
             print(json.dumps(res))
         return
@@ -471,22 +478,25 @@ def main():
     nvox = ne[0] * ne[1] * ne[2]
     dumped = dump_outputs(out, args.dump_outputs) if args.dump_outputs else None
 
-    kernel_s = time_apply(tps, u, args.steps, 1)
-    ab = algorithmic_bytes(ne)
-    # HBM bytes per launch by the PMC counters: collected in separate rocprofv3 --pmc passes (FETCH_SIZE x 2, WRITE_SIZE; the
-    # guide's gfx950 correction) and committed under profiles/ -- NOT measured inside this run; the source is named in the line
-    traffic, traffic_source = None, None
-    prof = os.path.join(ROOT, "profiles", "apply_traffic.json")
-    if os.path.exists(prof):
-        with open(prof) as fh:
-            t = json.load(fh)
-        if t.get("grid") == list(ne):
-            traffic, traffic_source = t.get("hbm_bytes_per_launch"), "from profile " + str(t.get("source"))
-    roofline = {"bound": "hbm", "achieved": ab / kernel_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": ab / kernel_s / 1e9 / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                "kernel": "vfem::k_apply_dma", "algorithmic_bytes_per_launch": ab, "kernel_ms": kernel_s * 1e3}
+    roofline = None
+    if args.full:
+        kernel_s = time_apply(tps, u, args.steps, 1)
+        ab = algorithmic_bytes(ne)
+        # HBM bytes per launch by the PMC counters: collected in separate rocprofv3 --pmc passes (FETCH_SIZE x 2, WRITE_SIZE; the
+        # guide's gfx950 correction) and committed under profiles/ -- NOT measured inside this run; the source is named in the line
+        traffic, traffic_source = None, None
+        prof = os.path.join(ROOT, "profiles", "apply_traffic.json")
+        if os.path.exists(prof):
+            with open(prof) as fh:
+                t = json.load(fh)
+            if t.get("grid") == list(ne):
+                traffic, traffic_source = t.get("hbm_bytes_per_launch"), "from profile " + str(t.get("source"))
+        roofline = {"bound": "hbm", "achieved": ab / kernel_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": ab / kernel_s / 1e9 / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                    "kernel": "vfem::k_apply_dma", "algorithmic_bytes_per_launch": ab, "kernel_ms": kernel_s * 1e3}
     del out
-    roofline["same_device_streaming"] = hbm_stream_calibration(3 * (ne[0] + 1) * (ne[1] + 1) * (ne[2] + 1) * 8)
+    if args.full:
+        roofline["same_device_streaming"] = hbm_stream_calibration(3 * (ne[0] + 1) * (ne[1] + 1) * (ne[2] + 1) * 8)
 
     result = {
         "metric": "matrix-free SpMV GVoxel/s (Q1 fp64, %dx%dx%d); CG-MG iterations/s reported in cg_mg" % ne,
@@ -496,11 +506,12 @@ def main():
         "config": {"workload": "K(rho) u on a %dx%dx%d voxel grid, trilinear hexahedra, fp64, seeded U[0,1] densities "
                                "(SIMP p=3, Emin=1e-4), u ~ N(0,1)" % ne,
                    "grid": list(ne), "parallelism": "1 GPU"},
-        "roofline": roofline,
     }
+    if roofline is not None:
+        result["roofline"] = roofline
     if dumped is not None:
         result["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
-    if not args.no_cg:
+    if args.full and not args.no_cg:
         del u, tps
         torch.cuda.empty_cache()
         result["spmv_other_grids"] = [spmv_rate((256, 256, 256))]
@@ -530,12 +541,12 @@ def main():
                 result["degree2_spmv"].append(degree2_rate(q2ne))
             except RuntimeError as e:
                 result["degree2_spmv"].append({"grid": "%dx%dx%d" % q2ne, "error": str(e)})
-    if args.rank_proxy > 1:
+    if args.full and args.rank_proxy > 1:
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import rank_proxy
         torch.cuda.empty_cache()
         result["rank_proxy"] = rank_proxy.run(args.rank_proxy)
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         torch.cuda.synchronize()
         result["cpu_baseline"] = cpu_baseline((160, 160, 160))
     print(json.dumps(result))

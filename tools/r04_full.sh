@@ -6,7 +6,7 @@ cd $R
 O=$R/gpurun_out/r04_full; mkdir -p $O
 step() { "$@"; rc=$?; if [ $rc -ge 124 ]; then echo "step killed/timed out (rc $rc): $*"; exit $rc; fi; return 0; }
 step timeout -k 10 1500 python -m pytest tests/ -q -m gpu -x --durations=15 > $O/tests.log 2>&1; tail -n 30 $O/tests.log
-step timeout -k 10 900 python bench.py --no-cpu > $O/bench.json 2> $O/bench.err; python3 - $O/bench.json <<'PY'
+step timeout -k 10 900 python bench.py --full --no-cpu > $O/bench.json 2> $O/bench.err; python3 - $O/bench.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().split("\n")[-1])
 print("value", d["value"], "ms", d["ms_per_step"], "frac", d["roofline"]["frac"])
