@@ -310,6 +310,13 @@ int vfem_gmg_pcg(vfem_gmg *mg, double *x, const double *b, int max_iter, double 
  * clip(x0 sqrt(dJ/(dc lambda)), max(x0-m,0), min(x0+m,1)) of OCOptimizer::step (OptimalityCriterion.hh:47-50); where
  * dJ/(dc lambda) < 0 the candidate is the lower edge max(x0-m,0) (the reference: NaN).  vfem_mean refuses n < 1. */
 int vfem_box_filter(const int64_t n_host[3], int radius, const double *in, double *out, int transpose, void *stream);
+/* The box filter on an x-slab: `in` holds the layers [x_first, x_first + n_local[0]) of a grid of nx_global x-layers (n_local[1],
+ * n_local[2] are the global y, z extents); the local layers [out_first, out_first + out_layers) are written to `out` (out_layers
+ * layers).  Neighbourhoods and row counts are clipped to the global grid, so the result equals the matching slice of
+ * vfem_box_filter on the whole grid bit for bit.  Refused (nothing read): a negative radius, local or output layers outside
+ * their ranges, and a written layer whose neighbour layers inside the global grid are not all local (too few ghost layers). */
+int vfem_box_filter_slab(const int64_t n_local[3], int64_t x_first, int64_t nx_global, int64_t out_first, int64_t out_layers,
+                         int radius, const double *in, double *out, int transpose, void *stream);
 int vfem_projection(int64_t n, double beta, const double *x, double *out, void *stream);
 int vfem_projection_backprop(int64_t n, double beta, const double *g, const double *vars, double *out, void *stream);
 int vfem_oc_candidate(int64_t n, const double *x0, const double *dJ, const double *dc, double lambda, double move, double *out,

@@ -129,6 +129,8 @@ SIGNATURES = {
     "vfem_gmg_pcg": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_int, c_int, c_int, RESIDUAL_CB, c_void_p,
                              POINTER(c_int), POINTER(c_double), c_void_p]),
     "vfem_box_filter": (c_int, [POINTER(c_int64), c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "vfem_box_filter_slab": (c_int, [POINTER(c_int64), c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int,
+                                     c_void_p]),
     "vfem_projection": (c_int, [c_int64, c_double, c_void_p, c_void_p, c_void_p]),
     "vfem_projection_backprop": (c_int, [c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vfem_oc_candidate": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p]),

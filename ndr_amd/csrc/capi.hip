@@ -1259,6 +1259,29 @@ int vfem_box_filter(const int64_t n[3], int radius, const double *in, double *ou
     launch_box_filter((int) n[0], (int) n[1], (int) n[2], radius, in, out, transpose, S(stream));
     VFEM_CATCH
 }
+int vfem_box_filter_slab(const int64_t n_local[3], int64_t x_first, int64_t nx_global, int64_t out_first, int64_t out_layers,
+                         int radius, const double *in, double *out, int transpose, void *stream) {
+    VFEM_TRY
+    if (radius < 0) throw Error("negative filter radius");
+    for (int d = 0; d < 3; ++d)
+        if (n_local[d] < 1 || n_local[d] > (1 << 30)) throw Error("vfem_box_filter_slab: invalid slab dimensions");
+    if (nx_global > (1 << 30) || x_first < 0 || x_first + n_local[0] > nx_global)
+        throw Error("vfem_box_filter_slab: the local layers do not lie in the global grid");
+    if (out_first < 0 || out_layers < 0 || out_first + out_layers > n_local[0])
+        throw Error("vfem_box_filter_slab: the output layers do not lie in the local layers");
+    if (radius > (1 << 30)) throw Error("vfem_box_filter_slab: radius too large");
+    auto width = [&](int64_t n) { return std::min<int64_t>(2 * (int64_t) radius + 1, n); };
+    if (width(nx_global) * width(n_local[1]) * width(n_local[2]) > INT32_MAX)
+        throw Error("vfem_box_filter_slab: neighbourhood too large");
+    if (out_layers == 0) return 0;
+    // every neighbour layer of a written layer that lies in the global grid must lie in the local layers
+    const int64_t g0 = x_first + out_first, g1 = g0 + out_layers - 1;
+    if (std::max<int64_t>(g0 - radius, 0) < x_first || std::min<int64_t>(g1 + radius, nx_global - 1) > x_first + n_local[0] - 1)
+        throw Error("vfem_box_filter_slab: the neighbourhood of a written layer leaves the local layers (too few ghost layers)");
+    launch_box_filter_slab((int) n_local[0], (int) n_local[1], (int) n_local[2], (int) x_first, (int) nx_global, (int) out_first,
+                           (int) out_layers, radius, in, out, transpose, S(stream));
+    VFEM_CATCH
+}
 int vfem_projection(int64_t n, double beta, const double *x, double *out, void *stream) {
     VFEM_TRY
     if (!(beta > 0)) throw Error("Beta parameter has to be positive (received beta = " + std::to_string(beta) + ")");

@@ -299,20 +299,25 @@ namespace vfem {
 // box filter of radius r clipped to the grid; every output row is normalised by its in-bounds neighbour count.
 // transpose = 0:  out_i = (1/c_i) sum_{k in N(i)} in_k        (A x)
 // transpose = 1:  out_k = sum_{i in N(k)} in_i / c_i          (A^T g; the neighbourhood relation is symmetric)
-__global__ void __launch_bounds__(256) k_box_filter(int nx, int ny, int nz, int r, const double *__restrict__ in,
+// `in` holds the x-layers [x_first, x_first + nx) of a grid of nx_global layers (an x-slab); the kernel writes the local
+// layers [out_first, out_first + out_layers) to `out` (out_layers layers).  Neighbourhoods and the counts c_i are clipped to the GLOBAL
+// grid, so a slab whose written layers have their r neighbour layers in `in` gives the matching slice of the whole-grid result bit
+// for bit (same loop order, same single division); the whole grid is x_first = 0, nx_global = nx, out_first = 0, out_layers = nx.
+__global__ void __launch_bounds__(256) k_box_filter(int ny, int nz, int x_first, int nx_global, int out_first,
+                                                    int out_layers, int r, const double *__restrict__ in,
                                                     double *__restrict__ out, int transpose) {
-    const long long n = (long long) nx * ny * nz;
+    const long long n = (long long) out_layers * ny * nz;
     for (long long e = (long long) blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long) gridDim.x * blockDim.x) {
-        const int k = (int) (e % nz), j = (int) ((e / nz) % ny), i = (int) (e / ((long long) nz * ny));
-        const int i0 = max(i - r, 0), i1 = min(i + r, nx - 1), j0 = max(j - r, 0), j1 = min(j + r, ny - 1);
+        const int k = (int) (e % nz), j = (int) ((e / nz) % ny), i = x_first + out_first + (int) (e / ((long long) nz * ny));
+        const int i0 = max(i - r, 0), i1 = min(i + r, nx_global - 1), j0 = max(j - r, 0), j1 = min(j + r, ny - 1);
         const int k0 = max(k - r, 0), k1 = min(k + r, nz - 1);
         double acc = 0.0;
         for (int a = i0; a <= i1; ++a)
             for (int b = j0; b <= j1; ++b)
                 for (int c = k0; c <= k1; ++c) {
-                    double v = in[((long long) a * ny + b) * nz + c];
+                    double v = in[((long long) (a - x_first) * ny + b) * nz + c];
                     if (transpose) {
-                        const int ca = min(a + r, nx - 1) - max(a - r, 0) + 1, cb = min(b + r, ny - 1) - max(b - r, 0) + 1;
+                        const int ca = min(a + r, nx_global - 1) - max(a - r, 0) + 1, cb = min(b + r, ny - 1) - max(b - r, 0) + 1;
                         const int cc = min(c + r, nz - 1) - max(c - r, 0) + 1;
                         v /= (double) (ca * cb * cc);
                     }
@@ -323,7 +328,12 @@ __global__ void __launch_bounds__(256) k_box_filter(int nx, int ny, int nz, int 
     }
 }
 void launch_box_filter(int nx, int ny, int nz, int r, const double *in, double *out, int transpose, hipStream_t s) {
-    k_box_filter<<<grid_for((long long) nx * ny * nz, 256), 256, 0, s>>>(nx, ny, nz, r, in, out, transpose);
+    launch_box_filter_slab(nx, ny, nz, 0, nx, 0, nx, r, in, out, transpose, s);
+}
+void launch_box_filter_slab(int nx, int ny, int nz, int x_first, int nx_global, int out_first, int out_layers, int r,
+                            const double *in, double *out, int transpose, hipStream_t s) {
+    k_box_filter<<<grid_for((long long) out_layers * ny * nz, 256), 256, 0, s>>>(ny, nz, x_first, nx_global, out_first, out_layers,
+                                                                                 r, in, out, transpose);
     VFEM_HIP(hipGetLastError());
 }
 
