@@ -199,6 +199,34 @@ int vfem_mg_coarsest_solve(vfem_mg *mg, const double *b, double *x, void *stream
  * order: the same matrix gives the same inverse bit for bit in every run.  Fails ("not positive definite") on a pivot <= 0. */
 int vfem_dense_spd_inverse(int64_t n, double *A, void *stream);
 
+/* ---- direct solve: band Cholesky (band_spd.hip; the reference's TPS::solve, TPS.hh:834-865, factorises with CHOLMOD) ----
+ * Band layout of an n x n symmetric positive definite matrix A of half-bandwidth w (A[i][j] = 0 for |i - j| > w), lower band in
+ * 64 x 64 tiles: nb = ceil(n / 64) tile rows, bt = ceil(w / 64); tile row I holds bt + 2 tiles of 4096 doubles (row-major).  Slot
+ * d = 0..bt is the tile A[64 I + r][64 (I - d) + c] (r, c < 64); slot bt + 1 belongs to the factorisation (its input is ignored, the
+ * factor leaves L_II^-1 there).  A[i][j], j <= i <= j + w, is
+ *     band[((i / 64) (bt + 2) + i / 64 - j / 64) 4096 + (i % 64) 64 + j % 64],
+ * nb (bt + 2) 4096 doubles in all.  Stored entries above the diagonal, outside the band, left of column 0 or in the padding rows
+ * i >= n are not read: vfem_band_spd_factor overwrites them (0; 1 on the padding diagonal).
+ *   vfem_band_spd_factor  A = L L^T in place (L in the lower band, same layout).  Fails with "band matrix is not positive definite
+ *                         (pivot k of n)", k the 1-based index of the first pivot <= 0.  Synchronises the stream.
+ *   vfem_band_spd_solve   x [nrhs][n] (right-hand sides in, solutions out) <- A^-1 x from the factor.
+ * Own kernels, no atomics, fixed summation order: the same matrix gives the same bits on every run.  The factorisation is 3 launches
+ * per tile row (1 in the last), the solve 2 per right-hand side.
+ * vfem_sim_direct_solve / vfem_gsim_direct_solve: u = K^-1 f on the free dofs, 0 on the fixed ones (f is ignored there).  The band
+ * of the full-size K, a fixed dof's row and column replaced by the identity, is assembled on the device from K0, the SIMP moduli and
+ * the Dirichlet mask, factorised, and kept in the handle until the densities, the SIMP parameters, the material or the Dirichlet
+ * conditions change (the reference's m_numericFactorizationUpToDate).  Half-bandwidth w = N d + N - 1 dofs, d = sum over the axes of
+ * p x the node stride of the axis.  Nonzero Dirichlet values are refused.  *_direct_factorizations: factorisations done so far;
+ * *_direct_band_bytes: the band storage a factorisation of this handle holds. */
+int vfem_band_spd_factor(int64_t n, int64_t w, double *band, void *stream);
+int vfem_band_spd_solve(int64_t n, int64_t w, const double *factor, double *x, int64_t nrhs, void *stream);
+int vfem_sim_direct_solve(vfem_sim *sim, const double *f, double *u, void *stream);
+int64_t vfem_sim_direct_factorizations(const vfem_sim *sim);
+int64_t vfem_sim_direct_band_bytes(const vfem_sim *sim);
+int vfem_gsim_direct_solve(vfem_gsim *sim, const double *f, double *u, void *stream);
+int64_t vfem_gsim_direct_factorizations(const vfem_gsim *sim);
+int64_t vfem_gsim_direct_band_bytes(const vfem_gsim *sim);
+
 /* MG::solve (MG.hh:447-472): numSteps V-cycles (first one a full-multigrid cycle if fmg) on K x = f
  * starting from x (in/out). */
 int vfem_mg_solve(vfem_mg *mg, double *x, const double *f, int num_steps, int num_smoothing_steps,

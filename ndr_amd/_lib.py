@@ -74,6 +74,14 @@ SIGNATURES = {
     "vfem_mg_interpolate": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "vfem_mg_coarsest_solve": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "vfem_dense_spd_inverse": (c_int, [c_int64, c_void_p, c_void_p]),
+    "vfem_band_spd_factor": (c_int, [c_int64, c_int64, c_void_p, c_void_p]),
+    "vfem_band_spd_solve": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "vfem_sim_direct_solve": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vfem_sim_direct_factorizations": (c_int64, [c_void_p]),
+    "vfem_sim_direct_band_bytes": (c_int64, [c_void_p]),
+    "vfem_gsim_direct_solve": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vfem_gsim_direct_factorizations": (c_int64, [c_void_p]),
+    "vfem_gsim_direct_band_bytes": (c_int64, [c_void_p]),
     "vfem_mg_solve": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "vfem_mg_pcg": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_int, c_int, c_int,
                             RESIDUAL_CB, c_void_p, POINTER(c_int), POINTER(c_double), c_void_p]),

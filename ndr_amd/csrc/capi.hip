@@ -946,6 +946,35 @@ int vfem_dense_spd_inverse(int64_t n, double *A, void *stream) {
     VFEM_HIP(hipStreamSynchronize(S(stream)));      // the workspace is released on return
     VFEM_CATCH
 }
+int vfem_band_spd_factor(int64_t n, int64_t w, double *band, void *stream) {
+    VFEM_TRY
+    if (n < 1 || w < 0 || w >= n) throw Error("band factorisation: n >= 1 and 0 <= w < n required");
+    DevBuf<int> info;
+    info.alloc(1);
+    launch_band_clean(n, w, band, S(stream));
+    band_spd_factor(n, w, band, info.p, S(stream), "band matrix");
+    VFEM_CATCH
+}
+int vfem_band_spd_solve(int64_t n, int64_t w, const double *factor, double *x, int64_t nrhs, void *stream) {
+    VFEM_TRY
+    if (n < 1 || w < 0 || w >= n || nrhs < 0) throw Error("band solve: n >= 1, 0 <= w < n and nrhs >= 0 required");
+    band_spd_solve(n, w, factor, x, nrhs, S(stream));
+    VFEM_CATCH
+}
+int vfem_sim_direct_solve(vfem_sim *sim, const double *f, double *u, void *stream) {
+    VFEM_TRY
+    if (sim->nonzero_dirichlet) throw Error("Nonzero Dirichlet constraints currently unsupported");
+    const int ne[3] = {sim->d.nx, sim->d.ny, sim->d.nz};
+    band_direct_solve(sim->direct, sim->operator_version, 3, 1, ne, sim->dK0.p, sim->Ep(), sim->dmask.p, f, u, S(stream));
+    VFEM_CATCH
+}
+int64_t vfem_sim_direct_factorizations(const vfem_sim *sim) { return sim->direct.factorizations; }
+int64_t vfem_sim_direct_band_bytes(const vfem_sim *sim) {
+    const int ne[3] = {sim->d.nx, sim->d.ny, sim->d.nz};
+    long long n, w;
+    band_geometry(3, 1, ne, n, w);
+    return band_spd_doubles(n, w) * (int64_t) sizeof(double);
+}
 int vfem_mg_coarsest_solve(vfem_mg *mg, const double *b, double *x, void *stream) {
     VFEM_TRY
     update_operators(mg, S(stream));

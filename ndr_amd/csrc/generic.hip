@@ -649,6 +649,9 @@ struct vfem_gsim {
     int q2_impl = 0;                               // vfem_gsim_set_option(6, v): 0 marching kernel (mode space), 1 dense gather kernel (cross-check), 2 pencil kernel
     DevBuf<uint8_t> dmask;
     std::vector<uint8_t> hmask;
+    bool nonzero_dirichlet = false;
+    long long operator_version = 1;                // bumped whenever K changes (densities, SIMP law, material, Dirichlet mask)
+    BandSolver direct;                             // factorisation of TPS::solve (vfem_gsim_direct_solve)
     // slab decomposition: element layers (axis 0) stored below / above the node grid; they only feed the Galerkin
     // element matrices of the ghost elements of coarser levels.  rho / E hold ex_lo + ne[0] + ex_hi layers.
     long long ex_lo = 0, ex_hi = 0;
@@ -1161,11 +1164,13 @@ int vfem_gsim_set_isotropic(vfem_gsim *sim, double young, double poisson) {
                                 : poisson * young / ((1.0 + poisson) * (1.0 - 2.0 * poisson));
     sim->mu = young / (2.0 + 2.0 * poisson);
     sim->update_k0();
+    ++sim->operator_version;
     G_CATCH
 }
 int vfem_gsim_set_simp(vfem_gsim *sim, double E0, double Emin, double gamma) {
     G_TRY
     sim->E0 = E0; sim->Emin = Emin; sim->gamma = gamma;
+    ++sim->operator_version;
     sim->update_E(nullptr);
     VFEM_HIP(hipDeviceSynchronize());
     G_CATCH
@@ -1176,6 +1181,11 @@ int vfem_gsim_k0(const vfem_gsim *sim, double *K0_host) {
 int vfem_gsim_set_dirichlet(vfem_gsim *sim, const uint8_t *mask_host, const double *values_host) {
     G_TRY
     sim->hmask.assign(mask_host, mask_host + sim->d.nnodes);
+    sim->nonzero_dirichlet = false;
+    for (long long n = 0; n < sim->d.nnodes; ++n)
+        for (int c = 0; c < sim->d.N; ++c)
+            if (((mask_host[n] >> c) & 1) && values_host[(size_t) n * sim->d.N + c] != 0.0) sim->nonzero_dirichlet = true;
+    ++sim->operator_version;
     VFEM_HIP(hipMemcpy(sim->dmask.p, mask_host, (size_t) sim->d.nnodes, hipMemcpyHostToDevice));
     VFEM_HIP(hipMemcpy(sim->dvals.p, values_host, (size_t) sim->d.nnodes * sim->d.N * sizeof(double), hipMemcpyHostToDevice));
     G_CATCH
@@ -1184,6 +1194,7 @@ int vfem_gsim_set_densities(vfem_gsim *sim, const double *rho, void *stream) {
     G_TRY
     // padded simulators take all stored layers (ex_lo + ne[0] + ex_hi), x slowest
     VFEM_HIP(hipMemcpyAsync(sim->rho.p, rho, (size_t) sim->stored_elems() * sizeof(double), hipMemcpyDeviceToDevice, GS(stream)));
+    ++sim->operator_version;
     sim->update_E(GS(stream));
     G_CATCH
 }
@@ -1212,6 +1223,19 @@ int vfem_gsim_apply_k(const vfem_gsim *sim, const double *u, double *out, void *
     else
         g_apply(sim->d, sim->dK0.p, 0, sim->E_local(), u, nullptr, nullptr, 0, out, GS(stream));
     G_CATCH
+}
+int vfem_gsim_direct_solve(vfem_gsim *sim, const double *f, double *u, void *stream) {
+    G_TRY
+    if (sim->nonzero_dirichlet) throw Error("Nonzero Dirichlet constraints currently unsupported");
+    band_direct_solve(sim->direct, sim->operator_version, sim->d.N, sim->d.p, sim->d.ne, sim->dK0.p, sim->E_local(), sim->dmask.p, f, u,
+                      GS(stream));
+    G_CATCH
+}
+int64_t vfem_gsim_direct_factorizations(const vfem_gsim *sim) { return sim->direct.factorizations; }
+int64_t vfem_gsim_direct_band_bytes(const vfem_gsim *sim) {
+    long long n, w;
+    band_geometry(sim->d.N, sim->d.p, sim->d.ne, n, w);
+    return band_spd_doubles(n, w) * (int64_t) sizeof(double);
 }
 int vfem_gsim_compliance_gradient(const vfem_gsim *sim, const double *u, double *g, void *stream) {
     G_TRY

@@ -226,6 +226,23 @@ void launch_q2_residual_fix(long long nn, const double *b, const uint8_t *mask, 
 void launch_gradient_q2(int nx, int ny, int nz, const double *K0, const double *rho, double E0, double Emin, double gamma,
                         const double *u, double *g, hipStream_t s);
 
+// Band Cholesky direct solve (band_spd.hip; layout in include/vfem.h).  A simulator keeps the factor of its K until the operator
+// changes (the reference's m_numericFactorizationUpToDate, TPS.hh:834-865).
+struct BandSolver {
+    DevBuf<double> band;
+    DevBuf<int> info;
+    long long version = 0;          // operator version the factor belongs to (0: none)
+    long long factorizations = 0;
+};
+void band_geometry(int N, int p, const int ne[3], long long &n, long long &w);     // dofs, half-bandwidth in dofs
+long long band_spd_doubles(long long n, long long w);
+void launch_band_clean(long long n, long long w, double *band, hipStream_t s);
+void band_spd_factor(long long n, long long w, double *band, int *info_dev, hipStream_t s, const char *what);   // synchronises s
+void band_spd_solve(long long n, long long w, const double *factor, double *x, long long nrhs, hipStream_t s);
+// u = K^-1 f with 0 at the fixed dofs; assembles and factorises first when bs.version != version
+void band_direct_solve(BandSolver &bs, long long version, int N, int p, const int ne[3], const double *K0, const double *E,
+                       const uint8_t *mask, const double *f, double *u, hipStream_t s);
+
 struct MlpArgs;
 void launch_mlp_forward(const MlpArgs &a, hipStream_t s);
 void launch_f32_to_f16(long long n, const float *in, void *out, hipStream_t s);
@@ -269,6 +286,7 @@ struct vfem_sim {
     long long operator_version = 1;             // bumped whenever K(rho) changes (densities, SIMP law, material): hierarchies rebuild
     vfem::Tuning tune;
     vfem::DevBuf<double> red;                   // scratch of the reductions (vfem_compliance)
+    vfem::BandSolver direct;                    // factorisation of TPS::solve (vfem_sim_direct_solve)
     long long n_store() const { return (long long) (d.nx + ex_lo + ex_hi) * d.ny * d.nz; }
     const double *Ep() const { return E.p + ex_lo * d.ny * d.nz; }
     const double *rhop() const { return rho.p + ex_lo * d.ny * d.nz; }

@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import band as _band
 
 __all__ = [
     "TensorProductSimulator", "TopologyOptimizationProblem", "ComplianceObjective",
@@ -199,6 +200,15 @@ def _densities_from_msh(path, field, ne, N):
     rho = np.zeros(nel)
     rho[np.ravel_multi_index(tuple(cell.T), tuple(int(n) for n in ne))] = values
     return rho
+
+
+def _factorize(mode, band_bytes):
+    """``directSolver`` of the simulators: True = band Cholesky of K, False = the multigrid-preconditioned CG stand-in"""
+    if mode == "auto":
+        return band_bytes <= _band.BAND_CAP_BYTES
+    if mode not in ("cholesky", "pcg"):
+        raise RuntimeError("directSolver must be 'auto', 'cholesky' or 'pcg', not %r" % (mode,))
+    return mode == "cholesky"
 
 
 # ----------------------------------------------------------------------------------------------
@@ -495,23 +505,43 @@ class TensorProductSimulator1_1_1:
             lv += 1
         return lv
 
-    def solve(self, f):
-        """TPS::solve (TPS.hh:834-865).  The reference factorises with CHOLMOD; here the same system is
-        solved by multigrid-preconditioned CG driven to a relative residual of 1e-11."""
+    # TPS::solve's method: "auto" factorises K (band Cholesky, vfem_sim_direct_solve) when its band fits in band.BAND_CAP_BYTES
+    # (8 GiB, a fixed cap: the choice depends on the grid only) and runs the multigrid-preconditioned CG stand-in above it;
+    # "cholesky" and "pcg" force one of the two
+    directSolver = "auto"
+
+    def directBandBytes(self):
+        return int(self._lib.vfem_sim_direct_band_bytes(self._h))
+
+    def numDirectFactorizations(self):
+        return int(self._lib.vfem_sim_direct_factorizations(self._h))
+
+    def solve_device(self, f):
+        """TPS::solve (TPS.hh:834-865) on the device: u = K^-1 f, 0 at the Dirichlet components.  The band Cholesky factor of K is
+        kept until the operator changes, as the reference keeps its CHOLMOD factor; the stand-in is MG-PCG to a relative residual
+        of 1e-11."""
         if np.any(self._dvals[self._mask] != 0):
             raise RuntimeError("Nonzero Dirichlet constraints currently unsupported")
+        f = _to_dev(f, (self.numNodes(), 3))
+        if _factorize(self.directSolver, self.directBandBytes()):
+            u = torch.empty_like(f)
+            _lib.check(self._lib.vfem_sim_direct_solve(self._h, _ptr(f), _ptr(u), _stream()))
+            return u
         mg = getattr(self, "_direct_mg", None)
         if mg is None:
             mg = self.multigridSolver(self._direct_levels())
             self._direct_mg = mg
         u = mg.preconditionedConjugateGradient_device(torch.zeros((self.numNodes(), 3), dtype=torch.float64,
                                                                   device=_dev()),
-                                                      _to_dev(f, (self.numNodes(), 3)), 500, 1e-11, None, 1, 2, True)
+                                                      f, 500, 1e-11, None, 1, 2, True)
         if not mg.last_relative_residual <= 1e-11:
             raise RuntimeError("TensorProductSimulator.solve: the iterative solve that stands in for the direct factorisation "
                                "did not converge (relative residual %.3e after %d iterations)"
                                % (mg.last_relative_residual, mg.last_iterations))
-        return _to_np(u)
+        return u
+
+    def solve(self, f):
+        return _to_np(self.solve_device(f))
 
     def solveWithImposedLoads(self):
         return self.solve(self.buildLoadVector())
@@ -757,7 +787,7 @@ class ComplianceObjective1_1_1:
     def updateCache(self, xPhys):
         if xPhys is not None:
             self._sim.setElementDensities(xPhys)
-        self._u = _to_dev(self._sim.solve(self._f), self._f.shape)
+        self._u = self._sim.solve_device(self._f)
 
     def u(self):
         return _to_np(self._u)
@@ -1424,11 +1454,24 @@ class _GenericSimulator:
             lv += 1
         return lv
 
-    def solve(self, f):
-        """TPS::solve (TPS.hh:834-865).  The reference factorises with CHOLMOD; here the same system is solved by
-        multigrid-preconditioned CG driven to a relative residual of 1e-11 (the coarsest level is a dense Cholesky)."""
+    directSolver = "auto"        # as TensorProductSimulator1_1_1.directSolver
+
+    def directBandBytes(self):
+        return int(self._lib.vfem_gsim_direct_band_bytes(self._h))
+
+    def numDirectFactorizations(self):
+        return int(self._lib.vfem_gsim_direct_factorizations(self._h))
+
+    def solve_device(self, f):
+        """TPS::solve (TPS.hh:834-865) on the device, see ``TensorProductSimulator1_1_1.solve_device``.  The stand-in is MG-PCG to
+        1e-11 (plain CG on grids that cannot be coarsened)."""
         if np.any(self._dvals[self._mask] != 0):
             raise RuntimeError("Nonzero Dirichlet constraints currently unsupported")
+        f = _to_dev(f, (self.numNodes(), self.N))
+        if _factorize(self.directSolver, self.directBandBytes()):
+            u = torch.empty_like(f)
+            _lib.check(self._lib.vfem_gsim_direct_solve(self._h, _ptr(f), _ptr(u), _stream()))
+            return u
         mg = getattr(self, "_direct_mg", None)
         if mg is None:
             mg = self.multigridSolver(self._direct_levels())
@@ -1437,10 +1480,13 @@ class _GenericSimulator:
         plain = mg.L == 0 and self.numNodes() * self.N > 40000
         u = mg.preconditionedConjugateGradient_device(
             torch.zeros((self.numNodes(), self.N), dtype=torch.float64, device=_dev()),
-            _to_dev(f, (self.numNodes(), self.N)), 500000 if plain else 2000, 1e-11, None, 1, 0 if plain else 2, True)
+            f, 500000 if plain else 2000, 1e-11, None, 1, 0 if plain else 2, True)
         if mg.last_relative_residual > 1e-10:
             raise RuntimeError("direct-solve replacement did not converge (relative residual %g)" % mg.last_relative_residual)
-        return _to_np(u)
+        return u
+
+    def solve(self, f):
+        return _to_np(self.solve_device(f))
 
     def solveWithImposedLoads(self):
         return self.solve(self.buildLoadVector())
