@@ -250,19 +250,37 @@ def type_of_volume_constaint_satisfier(mode):
     return hard[mode]
 
 
+class _GlobalMean(autograd.Function):
+    """mean of a field held in parts by the ranks: one all-reduce of the local sum (and of the count).  Every rank computes the
+    same loss from it, so the incoming gradient is already the whole dL/dmean and d mean/dx_i = 1/n needs no reduction."""
+
+    @staticmethod
+    def forward(ctx, x, allsum):
+        with torch.no_grad():
+            n = float(allsum(torch.tensor([float(x.numel())], dtype=torch.float64, device=x.device))[0])
+            total = allsum(x.sum().reshape(1))[0]
+        ctx.n, ctx.shape = n, x.shape
+        return (total / n).to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        return (grad_output / ctx.n).expand(ctx.shape), None
+
+
 def satisfy_volume_constraint(density, max_volume, compliance_loss=None, mode='constrained_sigmoid', scaler_mode='clip',
-                              constant=500., **kwargs):
+                              constant=500., allsum=None, allmax=None, **kwargs):
     """fem.satisfy_volume_constraint (fem.py:257-309): hard modes return the constrained density, soft modes the weighted
-    volume penalty to add to the compliance"""
+    volume penalty to add to the compliance.  `allsum` / `allmax` (as in sigmoid_with_constrained_mean) make `density` one rank's
+    part of a sharded field: the volume is that of the whole field, and `compliance_loss` must then be the whole field's too"""
     max_volume = torch.as_tensor(max_volume, dtype=density.dtype, device=density.device)
     if mode == 'constrained_sigmoid':
-        return sigmoid_with_constrained_mean(density, max_volume, torch.sigmoid)
+        return sigmoid_with_constrained_mean(density, max_volume, torch.sigmoid, allsum, allmax)
     if mode == 'constrained_projection':
         projection = kwargs.get('projection')
         if projection is None:
             raise ValueError("constrained_projection needs projection=<callable>")
-        return sigmoid_with_constrained_mean(density, max_volume, projection)
-    current = density.mean()
+        return sigmoid_with_constrained_mean(density, max_volume, projection, allsum, allmax)
+    current = density.mean() if allsum is None else _GlobalMean.apply(density, allsum)
     zero = torch.zeros_like(current)
     eps = 1e-7
     if mode == 'add_mean':

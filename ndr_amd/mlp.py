@@ -262,6 +262,7 @@ class TrainableMLP(torch.nn.Module):
         self.sidelen, self.domain, self.voxel_range = None, None, None
         self.reduce_gradients = True
         self._adam_state, self._adam_t = None, 0
+        self._adam_hparams = (1e-3, (0.9, 0.999), 1e-8)          # lr, betas, eps of the last adam_step (or of a loaded state)
 
     def _linears(self):
         return [m for m in self.net if isinstance(m, torch.nn.Linear)]
@@ -322,6 +323,7 @@ class TrainableMLP(torch.nn.Module):
         ps = [p for p in self.parameters() if p.grad is not None]
         if self._adam_state is None:
             self._adam_state = {id(p): (torch.zeros_like(p), torch.zeros_like(p)) for p in self.parameters()}
+        self._adam_hparams = (float(lr), (float(betas[0]), float(betas[1])), float(eps))
         self._adam_t += 1
         lib = _lib.load()
         for p in ps:
@@ -329,3 +331,51 @@ class TrainableMLP(torch.nn.Module):
             g = p.grad.contiguous()
             _lib.check(lib.vfem_adam_step(p.numel(), _ptr(p.data), _ptr(g), _ptr(m), _ptr(v), float(lr), float(betas[0]),
                                           float(betas[1]), float(eps), self._adam_t, _stream()))
+
+    def optimizer_state_dict(self):
+        """the fused Adam state in the layout of ``torch.optim.Adam.state_dict()`` (state indexed by the position in
+        ``parameters()``, one param group), so the reference's ``utils.save_weights`` / ``load_weights`` checkpoints interchange"""
+        params = list(self.parameters())
+        lr, betas, eps = self._adam_hparams
+        groups = torch.optim.Adam(params, lr=lr, betas=betas, eps=eps).state_dict()["param_groups"]
+        state = {}
+        if self._adam_state is not None:
+            for i, p in enumerate(params):
+                m, v = self._adam_state[id(p)]
+                state[i] = {"step": torch.tensor(float(self._adam_t)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
+        return {"state": state, "param_groups": groups}
+
+    def load_optimizer_state_dict(self, sd):
+        """continue the fused Adam from a ``torch.optim.Adam.state_dict()`` (or ``optimizer_state_dict``) of these parameters:
+        moments and step count (so the bias correction too) are restored.  Refuses state the fused update cannot continue:
+        other shapes, weight_decay != 0, amsgrad, maximize, or parameters at different step counts"""
+        params = list(self.parameters())
+        groups = sd["param_groups"]
+        if sum(len(g["params"]) for g in groups) != len(params):
+            raise ValueError("optimizer state for %d parameters, the network has %d"
+                             % (sum(len(g["params"]) for g in groups), len(params)))
+        for g in groups:
+            if float(g.get("weight_decay", 0)) != 0:
+                raise ValueError("the fused Adam has no weight decay (state has weight_decay %s)" % g["weight_decay"])
+            if g.get("amsgrad", False) or g.get("maximize", False):
+                raise ValueError("the fused Adam is plain Adam (state has amsgrad or maximize set)")
+        order = [k for g in groups for k in g["params"]]
+        state = sd["state"]
+        if state and len(state) != len(params):
+            raise ValueError("optimizer state holds %d of the %d parameters; the fused Adam keeps all or none" % (len(state), len(params)))
+        adam, steps = {}, set()
+        for pos, k in enumerate(order):
+            if not state:
+                break
+            st, p = state[k], params[pos]
+            m, v = st["exp_avg"], st["exp_avg_sq"]
+            if tuple(m.shape) != tuple(p.shape) or tuple(v.shape) != tuple(p.shape):
+                raise ValueError("optimizer state of parameter %d has shape %s, the parameter %s" % (pos, tuple(m.shape), tuple(p.shape)))
+            steps.add(int(float(st["step"])))
+            adam[id(p)] = (m.detach().to(device=p.device, dtype=p.dtype).contiguous().clone(),
+                           v.detach().to(device=p.device, dtype=p.dtype).contiguous().clone())
+        if len(steps) > 1:
+            raise ValueError("the fused Adam keeps one step count; the state has %s" % sorted(steps))
+        g = groups[0]
+        self._adam_hparams = (float(g["lr"]), (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"]))
+        self._adam_state, self._adam_t = (adam, steps.pop()) if adam else (None, 0)
