@@ -15,6 +15,17 @@ _lib = None
 
 RESIDUAL_CB = ctypes.CFUNCTYPE(None, c_void_p, c_int, c_double)
 
+
+class _SL(ctypes.Structure):
+    """one level of a slab hierarchy (vfem_mg_create_slab, vfem_gmg_create_slab)"""
+    _fields_ = [("nx", c_int64), ("elem_extra_lo", c_int64), ("elem_extra_hi", c_int64), ("xshift", c_int64), ("xparity", ctypes.c_int32)]
+
+
+class _DL(ctypes.Structure):
+    """one distributed level as the slab PCG driver sees it (vfem_mg_pcg_slab)"""
+    _fields_ = [("n_planes", c_int64), ("plane_nodes", c_int64), ("first_owned", c_int64), ("last_owned", c_int64), ("xoffn", c_int64),
+                ("gl", ctypes.c_int32), ("gr", ctypes.c_int32), ("x", c_void_p), ("b", c_void_p), ("r", c_void_p)]
+
 # name -> (restype, argtypes); kept in one table so tests can check it against include/vfem.h
 SIGNATURES = {
     "vfem_last_error": (c_char_p, []),

@@ -11,12 +11,17 @@ Dot products count an interface plane once (the lower rank owns it).
 The per-rank numerics are behind `LocalOps`; the product implementation is `HipLocalOps` (libvfem kernels on
 device tensors).  Tests substitute an oracle-backed implementation to exercise this host logic on CPU.
 """
+import ctypes
 import os
 import time
 
 import numpy as np
 import torch
 import torch.distributed as dist
+
+from . import _lib, fem
+from .pyVoxelFEM import _ptr, _stream
+from .slab_comm import MAX, SlabComm
 
 
 class SlabPartition:
@@ -40,6 +45,7 @@ class SlabPartition:
         self.x0, self.x1 = starts[rank], starts[rank + 1]          # owned element layers [x0, x1)
         self.gl = 1 if rank > 0 else 0                              # ghost element layers
         self.gr = 1 if rank < world - 1 else 0
+        self.halo_width = 1                                         # ghost node planes per side
         self.local_ne = (self.x1 - self.x0 + self.gl + self.gr, self.ne[1], self.ne[2])
         self.plane = (self.ne[1] + 1) * (self.ne[2] + 1)            # nodes per x-plane
         self.n_planes = self.local_ne[0] + 1
@@ -56,6 +62,10 @@ class SlabPartition:
         hi[0] = bbmin[0] + (self.x1 + self.gr) * h
         return lo, hi
 
+    def layers(self):
+        """owned element layers of every rank"""
+        return [b - a for a, b in zip(self.starts, self.starts[1:])]
+
     def element_slice(self):
         """global element layers held locally (ghost layers included)"""
         return slice(self.x0 - self.gl, self.x1 + self.gr)
@@ -70,64 +80,32 @@ class SlabPartition:
 
 
 class HaloExchanger:
-    """Refreshes the ghost node planes of a nodal field [n_planes * plane, 3] from the neighbours."""
+    """Refreshes the ghost node planes of a nodal field [n_planes * plane, 3] from the neighbours: the plane indices of a
+    partition or level geometry `part` over `SlabComm`."""
 
-    def __init__(self, part, group=None, proxy=False):
+    def __init__(self, part, comm=None):
         self.p = part
-        self.group = group
-        self.proxy = proxy      # rank proxy (tools/rank_proxy.py): no peers exist; a message becomes a device copy of the same bytes
+        self.comm = comm or SlabComm()
+        self.messages = 0       # sent to (= received from) the neighbours; a rank proxy counts its device copies
 
     def start(self, field, left=True, right=True):
-        """Begin the exchange of the two interface planes with each neighbour (`left` / `right`: only that side) and return a
-        handle for `finish`.  The transfers
-        are posted as one batch of non-blocking sends / receives and run while the caller launches work that does not touch
-        the ghost planes (DistributedStiffness.apply: the interior planes).  The same code serves both backends: under nccl
-        (RCCL over xGMI) the plane views of the device tensor are sent as they are; under gloo (CPU tests, one-GPU
-        rehearsal) a device plane is staged through host memory first and copied back in `finish`."""
+        """Begin the exchange of the interface planes with each neighbour (`left` / `right`: only that side) and return a handle
+        for `finish`.  The transfers run while the caller launches work that does not touch the ghost planes
+        (DistributedStiffness.apply: the interior planes)."""
         p = self.p
-        if p.world == 1:
-            return None
         v = field.view(p.n_planes, -1)
-        w = getattr(p, "halo_width", 1)        # ghost node planes per side (degree-2 slabs: 4), contiguous in memory
-        if self.proxy:
-            # what a neighbour would have sent is replaced by this rank's own planes: the same number of bytes moves, on the device
-            n = 0
-            if p.gl and left:
-                v[p.first_owned - w:p.first_owned].copy_(v[p.first_owned + 1:p.first_owned + 1 + w]); n += 1
-            if p.gr and right:
-                v[p.last_owned + 1:p.last_owned + 1 + w].copy_(v[p.last_owned - w:p.last_owned]); n += 1
-            self.messages = getattr(self, "messages", 0) + n
-            return None
-        staged = field.is_cuda and dist.get_backend(self.group) == "gloo"
-        ops, recvs = [], []
-
-        def add(send_first, recv_first, peer):
-            send, recv = slice(send_first, send_first + w), slice(recv_first, recv_first + w)
-            sb = v[send].cpu() if staged else v[send]
-            rb = torch.empty_like(sb) if staged else v[recv]
-            ops.append(dist.P2POp(dist.isend, sb, peer, self.group))
-            ops.append(dist.P2POp(dist.irecv, rb, peer, self.group))
-            if staged:
-                recvs.append((recv, rb))
-
+        w = p.halo_width                       # ghost node planes per side (degree-2 slabs: 4), contiguous in memory
+        pairs = []
         if p.gl and left:   # left neighbour: send my planes first_owned+1 .., receive my ghost planes 0 ..
-            add(p.first_owned + 1, p.first_owned - w, p.rank - 1)
+            pairs.append((p.rank - 1, v[p.first_owned + 1:p.first_owned + 1 + w], v[p.first_owned - w:p.first_owned]))
         if p.gr and right:  # right neighbour: send my planes .. last_owned-1, receive my ghost planes last_owned+1 ..
-            add(p.last_owned - w, p.last_owned + 1, p.rank + 1)
-        if not ops:
-            return None
-        self.messages = getattr(self, "messages", 0) + len(ops) // 2
-        return dist.batch_isend_irecv(ops), recvs, v
+            pairs.append((p.rank + 1, v[p.last_owned - w:p.last_owned], v[p.last_owned + 1:p.last_owned + 1 + w]))
+        self.messages += len(pairs)
+        return self.comm.start(pairs) if pairs else None
 
     def finish(self, handle):
         """wait for the transfers of `start`; afterwards the ghost planes of the field hold the neighbours' values"""
-        if handle is None:
-            return
-        works, recvs, v = handle
-        for w in works:
-            w.wait()
-        for plane, rb in recvs:
-            v[plane].copy_(rb)
+        self.comm.finish(handle)
 
     def exchange(self, field):
         self.finish(self.start(field))
@@ -139,14 +117,7 @@ class HaloExchanger:
         av = a.view(p.n_planes, -1)[lo:hi]
         bv = b.view(p.n_planes, -1)[lo:hi]
         s = (av * bv).sum().reshape(1)
-        if p.world > 1 and not self.proxy:
-            if s.is_cuda and dist.get_backend(self.group) == "gloo":
-                h = s.cpu()
-                dist.all_reduce(h, group=self.group)
-                s = h.to(s.device)
-            else:
-                dist.all_reduce(s, group=self.group)
-        return s
+        return self.comm.all_reduce(s) if p.world > 1 else s
 
 
 class HipLocalOps:
@@ -156,7 +127,6 @@ class HipLocalOps:
         from . import pyVoxelFEM as pv
         lo, hi = part.local_bbox(bbmin, bbmax)
         self.tps = pv.TensorProductSimulator1_1_1([lo, hi], list(part.local_ne))
-        from . import _lib
         _lib.check(self.tps._lib.vfem_sim_set_isotropic(self.tps._h, young, poisson))
         self.tps.E_0, self.tps.E_min, self.tps.gamma = E0, Emin, gamma
         self.device = torch.device("cuda", torch.cuda.current_device())
@@ -169,8 +139,6 @@ class HipLocalOps:
 
     def apply_planes(self, u, out, lo, hi):
         """output node planes lo..hi (inclusive) only"""
-        from . import _lib
-        from .pyVoxelFEM import _ptr, _stream
         _lib.check(self.tps._lib.vfem_sim_apply_k_planes(self.tps._h, _ptr(u), _ptr(out), int(lo), int(hi), _stream()))
 
 
@@ -179,7 +147,7 @@ class DistributedStiffness:
 
     def __init__(self, part, ops, group=None):
         self.part, self.ops = part, ops
-        self.halo = HaloExchanger(part, group)
+        self.halo = HaloExchanger(part, SlabComm(group))
 
     def apply(self, u, exchange=True):
         p = self.part
@@ -265,12 +233,7 @@ def bench_pcg(ne, levels, tol=1e-4):
     t0 = time.perf_counter()
     u = ds.pcg(torch.zeros_like(f), f, 100, tol, 1, 2, True)
     torch.cuda.synchronize()
-    dt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
-    if dist.is_initialized():
-        if dist.get_backend() != "gloo":
-            dt = dt.cuda()
-        dist.all_reduce(dt, op=dist.ReduceOp.MAX)
-    dt = float(dt.item())
+    dt = float(ds.comm.all_reduce(torch.tensor([time.perf_counter() - t0], dtype=torch.float64), MAX).item())
     return {"grid": "%dx%dx%d" % tuple(ne), "levels": levels, "distributed_levels": ds.Ld + 1, "iterations": ds.last_iterations,
             "seconds": dt, "iterations_per_s": ds.last_iterations / dt, "relative_residual": ds.last_relative_residual,
             "compliance": 2.0 * ds.compliance(f, u), "densities": "sharded (owned layers per rank)" if sharded else "replicated",
@@ -282,7 +245,8 @@ def bench_mlp(side=(512, 256, 256), es=1024, nn_=512, nl=4, sigma=4.0, reps=3):
     slab (a contiguous voxel range) with replicated weights; time = max over ranks, voxels = the whole grid"""
     import numpy as np
     from .mlp import MLP
-    world, rank = dist.get_world_size(), dist.get_rank()
+    comm = SlabComm()
+    world, rank = comm.world, comm.rank
     rng = np.random.default_rng(88)
     B = (rng.standard_normal((es, 3)) * sigma).astype(np.float32)
     Ws = [rng.standard_normal((nn_, 2 * es)).astype(np.float32) / np.sqrt(2 * es)]
@@ -300,14 +264,8 @@ def bench_mlp(side=(512, 256, 256), es=1024, nn_=512, nl=4, sigma=4.0, reps=3):
     for _ in range(reps):
         out = m.forward_grid_range(side, x0 * plane, (x1 - x0) * plane)
     torch.cuda.synchronize()
-    dt = torch.tensor([(time.perf_counter() - t0) / reps], dtype=torch.float64)
-    chk = out.double().sum().reshape(1)
-    if dist.get_backend() != "gloo":
-        dt = dt.cuda()
-    else:
-        chk = chk.cpu()
-    dist.all_reduce(dt, op=dist.ReduceOp.MAX)
-    dist.all_reduce(chk)
+    dt = comm.all_reduce(torch.tensor([(time.perf_counter() - t0) / reps], dtype=torch.float64), MAX)
+    chk = comm.all_reduce(out.double().sum().reshape(1))
     nv = side[0] * plane
     flop = 2.0 * (3 * es + 2 * es * nn_ + (nl - 2) * nn_ * nn_ + nn_) * nv
     sec = float(dt.item())
@@ -334,7 +292,8 @@ def _bench_q2(world):
 def bench_apply(ne, steps, warmup, with_cg=True):
     """bench.py's N > 1 leg: K steps of {halo exchange + local apply}, max over ranks, whole-grid GVoxel/s."""
     init_process_group_from_env()
-    world, rank = dist.get_world_size(), dist.get_rank()
+    comm = SlabComm()
+    world, rank = comm.world, comm.rank
     part = SlabPartition(ne, world, rank, align=2)
     ops = HipLocalOps(part, [0, 0, 0], [1, 1, 1])
     ops.set_densities(seeded_slab_density(part).to(ops.device))
@@ -354,11 +313,7 @@ def bench_apply(ne, steps, warmup, with_cg=True):
     torch.cuda.synchronize()
     dist.barrier()
     torch.cuda.synchronize()
-    dt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
-    if dist.get_backend() != "gloo":
-        dt = dt.to(ops.device)
-    dist.all_reduce(dt, op=dist.ReduceOp.MAX)
-    wall = float(dt.item())
+    wall = float(comm.all_reduce(torch.tensor([time.perf_counter() - t0], dtype=torch.float64), MAX).item())
     chk = K.halo.dot(out, out)
     del out, u, K, ops
     torch.cuda.empty_cache()
@@ -402,38 +357,43 @@ def bench_apply(ne, steps, warmup, with_cg=True):
 # planes are refreshed; dot products count interface planes once and finish with one all-reduce.
 # ==============================================================================================
 
-def auto_dist_levels(nx, world, num_levels, min_layers=8):
+def auto_dist_levels(nx, world, num_levels, min_layers=8, max_levels=None):
     """Number of coarsenings that stay distributed (Ld; levels 0 .. Ld are slab-decomposed, the rest replicated): as many as leave a
     rank at least `min_layers` owned element layers on the deepest of them and keep every slab boundary on an even plane of the next
-    level.  Below that a level is launch-floor-bound whether distributed or replicated (rank proxy,
+    level, `max_levels` at the most.  Below that a level is launch-floor-bound whether distributed or replicated (rank proxy,
     profiles/r04_rank_proxy_levels512.jsonl: 20.6 / 20.1 / 20.0 ms per iteration with 4 / 5 / 6 distributed levels at 512^3 / 8) while
     every further level adds ~60 messages per iteration (138 / 202 / 278)."""
     ld = 0
-    while ld + 1 < num_levels and nx % (world * 2 ** (ld + 2)) == 0 and nx // (world * 2 ** (ld + 1)) >= min_layers:
+    while (ld + 1 < num_levels and (max_levels is None or ld < max_levels) and nx % (world * 2 ** (ld + 2)) == 0
+           and nx // (world * 2 ** (ld + 1)) >= min_layers):
         ld += 1
     return ld
 
 
-class _LevelGeom:
-    def __init__(self, part, l, Ld, ne0):
-        s = 2 ** l
+class LevelGeom:
+    """local grid of one rank on level l of a slab hierarchy of polynomial degree `degree` with `ghost` ghost element layers per
+    neighbour; planes are node planes of that level (`degree` per element layer)"""
+
+    def __init__(self, part, l, Ld, ne0, degree=1, ghost=1):
+        P, s = degree, 2 ** l
         self.l = l
+        self.rank, self.world = part.rank, part.world
         self.X0, self.X1 = part.x0 // s, part.x1 // s
-        self.gl, self.gr = part.gl, part.gr
+        self.gl, self.gr = (ghost if part.rank > 0 else 0), (ghost if part.rank < part.world - 1 else 0)   # ghost ELEMENT layers
         self.nx = self.X1 - self.X0 + self.gl + self.gr
         self.ny, self.nz = ne0[1] // s, ne0[2] // s
-        self.n_planes = self.nx + 1
-        self.plane = (self.ny + 1) * (self.nz + 1)
-        self.first_owned = self.gl
-        self.last_owned = self.gl + (self.X1 - self.X0)
-        self.xoffn = self.X0 - self.gl
-        pad = (2 ** (Ld - l) - 1) if l <= Ld else 0
-        self.extra_lo, self.extra_hi = self.gl * pad, self.gr * pad
-        self.xshift = -self.gl if l > 0 else 0
-        self.xparity = self.xoffn & 1
-        self.rank, self.world = part.rank, part.world
+        self.n_planes = P * self.nx + 1
+        self.plane = (P * self.ny + 1) * (P * self.nz + 1)
+        self.halo_width = P * ghost
+        self.first_owned = P * self.gl
+        self.last_owned = self.first_owned + P * (self.X1 - self.X0)
+        self.xoffe = self.X0 - self.gl                                       # global element layer of local layer 0
+        self.xoffn = P * self.xoffe                                          # global node plane of local plane 0
+        pad = ghost * (2 ** (Ld - l) - 1) if l <= Ld else 0
+        self.extra_lo, self.extra_hi = (pad if self.gl else 0), (pad if self.gr else 0)
+        self.xshift = -P * self.gl if l > 0 else 0                           # fine local plane = 2 * local plane + xshift
+        self.xparity = self.xoffe & 1
 
-    # HaloExchanger duck-typing
     def reduction_weight_planes(self):
         return self.first_owned, self.last_owned + (1 if self.rank == self.world - 1 else 0)
 
@@ -447,89 +407,90 @@ class DistributedMGSolver:
         GPU, tools/rank_proxy.py): every message becomes a device copy of the same size out of this rank's own planes and the
         all-reduces are skipped, so the VALUES are meaningless -- only the work, the launches and the host-side cost of one
         rank's iteration are those of the real run."""
-        import ctypes
-        from . import _lib
-        from . import pyVoxelFEM as pv
-        self._ct, self._lib_mod, self._pv = ctypes, _lib, pv
         self.lib = _lib.load()
-        self.group = group
-        self.proxy = proxy is not None
-        if self.proxy:
-            self.world, self.rank = int(proxy[0]), int(proxy[1])
-        else:
-            self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-            self.rank = dist.get_rank(group) if dist.is_initialized() else 0
+        # ranks and proxy
+        self.comm = SlabComm(group, proxy)
+        self.group, self.proxy, self.world, self.rank = group, self.comm.proxy, self.comm.world, self.comm.rank
+        # partition and geometry
         self.ne = tuple(int(v) for v in ne)
         self.L = int(num_levels)
         if dist_levels is None:
-            dist_levels = auto_dist_levels(self.ne[0], self.world, self.L, self.MIN_LAYERS)
+            dist_levels = auto_dist_levels(self.ne[0], self.world, self.L, self.MIN_LAYERS, self.MAX_AUTO_DIST_LEVELS)
         self.Ld = int(dist_levels)
         if self.Ld + 1 > self.L:
             raise RuntimeError("need at least one replicated level below the distributed ones")
         self.T = self.Ld + 1
         self.part = SlabPartition(self.ne, self.world, self.rank, align=2 ** (self.Ld + 1))
-        self.geom = [_LevelGeom(self.part, l, self.Ld, self.ne) for l in range(self.T + 1)]
+        if self.world > 1 and (self.part.x1 - self.part.x0) >> self.Ld < self.GHOST:       # (degree 1: the alignment rules it out)
+            raise RuntimeError("slab thinner than the ghost layers on the deepest distributed level")
+        self.geom = [LevelGeom(self.part, l, self.Ld, self.ne, self.DEGREE, self.GHOST) for l in range(self.T + 1)]
         self.dev = torch.device("cuda", torch.cuda.current_device())
 
-        # replicated (global) simulator + hierarchy: Dirichlet masks of every level, loads, coarse cycles
-        self.gsim = pv.TensorProductSimulator1_1_1([np.asarray(bbmin, float), np.asarray(bbmax, float)], list(self.ne))
-        self.gsim.readMaterial(material_path)
-        self.gsim.applyDisplacementsAndLoadsFromFile(bc_path)
-        self.gsim.E_0, self.gsim.E_min, self.gsim.gamma = E0, Emin, gamma
-        h = ctypes.c_void_p()
-        _lib.check(self.lib.vfem_mg_create_partial(ctypes.byref(h), self.gsim._h, self.L, self.T))
-        self.gmg = h
-
-        # local slab simulator (node grid: owned + ghost layers; element arrays padded)
+        # the replicated simulator + hierarchy (coarse cycles), the local slab simulator (node grid: owned + ghost layers; element
+        # arrays padded) and the Dirichlet masks of the local grids
+        def material(sim):
+            sim.readMaterial(material_path)
+            sim.E_0, sim.E_min, sim.gamma = E0, Emin, gamma
+            return sim
+        bbmin, bbmax = np.asarray(bbmin, float), np.asarray(bbmax, float)
         g0 = self.geom[0]
-        lo, hi = self.part.local_bbox(bbmin, bbmax)
-        _lib.check(self.lib.vfem_sim_set_next_element_padding(g0.extra_lo, g0.extra_hi))
-        self.lsim = pv.TensorProductSimulator1_1_1([lo, hi], [g0.nx, self.ne[1], self.ne[2]])
-        self.lsim.readMaterial(material_path)
-        self.lsim.E_0, self.lsim.E_min, self.lsim.gamma = E0, Emin, gamma
-
-        # per-level local Dirichlet masks = slices of the global coarsened masks
-        masks = []
-        for l, g in enumerate(self.geom):
-            nn = int(self.lib.vfem_mg_level_num_nodes(self.gmg, l))
-            m = np.empty(nn, dtype=np.uint8)
-            _lib.check(self.lib.vfem_mg_level_dirichlet_mask(self.gmg, l, m.ctypes.data_as(ctypes.c_void_p)))
-            m = m.reshape(-1, g.plane)[g.xoffn:g.xoffn + g.n_planes]
-            masks.append(np.ascontiguousarray(m.reshape(-1)))
-        self._masks = masks
+        h = (bbmax[0] - bbmin[0]) / self.ne[0]
+        lo, hi = bbmin.copy(), bbmax.copy()
+        lo[0], hi[0] = bbmin[0] + g0.xoffe * h, bbmin[0] + (g0.xoffe + g0.nx) * h
+        self._masks = masks = self._create_simulators(bbmin, bbmax, [lo, hi], bc_path, material)
         m0 = masks[0]
         self.lsim._mask = np.stack([(m0 >> c) & 1 for c in range(3)], axis=1).astype(bool)
         self.lsim._dvals = np.zeros((m0.size, 3))
         self.lsim._push_dirichlet()
 
-        class _SL(ctypes.Structure):
-            _fields_ = [("nx", ctypes.c_int64), ("elem_extra_lo", ctypes.c_int64), ("elem_extra_hi", ctypes.c_int64),
-                        ("xshift", ctypes.c_int64), ("xparity", ctypes.c_int32)]
-        arr = (_SL * len(self.geom))()
+        # slab hierarchy
+        arr = (_lib._SL * len(self.geom))()
         for l, g in enumerate(self.geom):
             arr[l].nx, arr[l].elem_extra_lo, arr[l].elem_extra_hi = g.nx, g.extra_lo, g.extra_hi
             arr[l].xshift, arr[l].xparity = g.xshift, g.xparity
         mptrs = (ctypes.c_void_p * len(masks))(*[m.ctypes.data_as(ctypes.c_void_p).value for m in masks])
-        h2 = ctypes.c_void_p()
-        _lib.check(self.lib.vfem_mg_create_slab(ctypes.byref(h2), self.lsim._h, len(self.geom), arr, mptrs))
-        self.lmg = h2
-        self.halos = [HaloExchanger(g, group, self.proxy) for g in self.geom]
-        for hx, g in zip(self.halos, self.geom):
-            hx.p.world, hx.p.rank = self.world, self.rank
+        self.lmg = ctypes.c_void_p()
+        _lib.check(self._mg("create_slab")(ctypes.byref(self.lmg), self.lsim._h, len(self.geom), arr, mptrs))
+
+        # halos and work vectors
+        self.halos = [HaloExchanger(g, self.comm) for g in self.geom]
         z = lambda g: torch.zeros((g.n_planes * g.plane, 3), dtype=torch.float64, device=self.dev)
         self.x = [z(g) for g in self.geom]
         self.b = [z(g) for g in self.geom]
         self.r = [z(g) for g in self.geom[:-1]]
-        gT = int(self.lib.vfem_mg_level_num_nodes(self.gmg, self.T))
+        gT = int(self._mg("level_num_nodes")(self.gmg, self._replicated_level()))
         self.xT = torch.zeros((gT, 3), dtype=torch.float64, device=self.dev)
         self.bT = torch.zeros((gT, 3), dtype=torch.float64, device=self.dev)
         self.symmetric_gs = True
-        self.overlap_sweeps = True          # relax interface planes first and exchange them behind the interior planes (where possible)
+        if self.PARITY_AWARE_HALO:
+            self.overlap_sweeps = True      # relax interface planes first and exchange them behind the interior planes (where possible)
         self.last_iterations, self.last_relative_residual = 0, 0.0
 
+    def _create_simulators(self, bbmin, bbmax, local_box, bc_path, material):
+        """the step of the constructor that depends on the degree: self.gsim, self.gmg (replicated), self.lsim (local slab);
+        returns the Dirichlet masks (flat uint8, bit c = component c) of the local grids of self.geom"""
+        from . import pyVoxelFEM as pv
+        # replicated (global) simulator + hierarchy: Dirichlet masks of every level, loads, coarse cycles
+        self.gsim = material(pv.TensorProductSimulator1_1_1([bbmin, bbmax], list(self.ne)))
+        self.gsim.applyDisplacementsAndLoadsFromFile(bc_path)
+        self.gmg = ctypes.c_void_p()
+        _lib.check(self.lib.vfem_mg_create_partial(ctypes.byref(self.gmg), self.gsim._h, self.L, self.T))
+        g0 = self.geom[0]
+        _lib.check(self.lib.vfem_sim_set_next_element_padding(g0.extra_lo, g0.extra_hi))
+        self.lsim = material(pv.TensorProductSimulator1_1_1(local_box, [g0.nx, self.ne[1], self.ne[2]]))
+        # per-level local Dirichlet masks = slices of the global coarsened masks
+        masks = []
+        for l, g in enumerate(self.geom):
+            m = np.empty(int(self.lib.vfem_mg_level_num_nodes(self.gmg, l)), dtype=np.uint8)
+            _lib.check(self.lib.vfem_mg_level_dirichlet_mask(self.gmg, l, m.ctypes.data_as(ctypes.c_void_p)))
+            m = m.reshape(-1, g.plane)[g.xoffn:g.xoffn + g.n_planes]
+            masks.append(np.ascontiguousarray(m.reshape(-1)))
+        return masks
+
     # ---- small helpers -------------------------------------------------------------------
-    proxy = False                  # (instances built as a rank proxy set it; subclasses with their own constructor inherit the default)
+    DEGREE, GHOST = 1, 1           # polynomial degree; ghost element layers per neighbour
     MIN_LAYERS = 8                 # owned element layers per rank on the deepest distributed level (automatic choice)
+    MAX_AUTO_DIST_LEVELS = None    # no cap on the automatic choice
     _MG_PREFIX = "vfem_mg_"        # C entry points of the hierarchy handles (the degree-2 subclass uses vfem_gmg_)
     KE_DOUBLES = 576               # doubles per element matrix of the first replicated level
     COLOR_GROUPS = ((0, 4), (4, 4))   # colours between two halo refreshes: all colours of one x index
@@ -548,24 +509,7 @@ class DistributedMGSolver:
         level 2 is built from the moduli)"""
         return self.T - 1 if self.T >= 3 else 0
 
-    def _s(self):
-        return self._ct.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-    def _p(self, t):
-        return self._ct.c_void_p(t.data_ptr())
-
-    def _chk(self, status):
-        self._lib_mod.check(status)
-
-    def _allreduce(self, t):
-        if self.world > 1 and not self.proxy:
-            if t.is_cuda and dist.get_backend(self.group) == "gloo":
-                h = t.cpu()
-                dist.all_reduce(h, group=self.group)
-                t.copy_(h)
-            else:
-                dist.all_reduce(t, group=self.group)
-        return t
+    _s, _p, _chk = staticmethod(_stream), staticmethod(_ptr), staticmethod(_lib.check)
 
     def local_loads(self):
         g = self.geom[0]
@@ -593,29 +537,14 @@ class DistributedMGSolver:
             raise RuntimeError("slab thinner than the padding of the local hierarchy")
         local = torch.empty((lo_need + own.shape[0] + hi_need, layer), dtype=torch.float64, device=own.device)
         local[lo_need:lo_need + own.shape[0]] = own
-        staged = own.is_cuda and self.world > 1 and not self.proxy and dist.get_backend(self.group) == "gloo"
-        ops, recvs = [], []
-
-        def add(send, recv_slice, peer):
-            if self.proxy:
-                local[recv_slice].copy_(send)
-                return
-            sb = send.contiguous().cpu() if staged else send.contiguous()
-            rb = torch.empty_like(sb) if staged else torch.empty_like(local[recv_slice])
-            ops.append(dist.P2POp(dist.isend, sb, peer, self.group))
-            ops.append(dist.P2POp(dist.irecv, rb, peer, self.group))
-            recvs.append((recv_slice, rb))
-
         # every interior interface needs the same number of layers on both sides (the padding depends on Ld only)
+        pairs, n = [], own.shape[0]
         if g.gl:
-            add(own[:lo_need], slice(0, lo_need), self.rank - 1)          # what the left neighbour needs from me = what I need from it
+            pairs.append((self.rank - 1, own[:lo_need], local[:lo_need]))   # what the left neighbour needs from me = what I need from it
         if g.gr:
-            add(own[own.shape[0] - hi_need:], slice(lo_need + own.shape[0], lo_need + own.shape[0] + hi_need), self.rank + 1)
-        if ops:
-            for w in dist.batch_isend_irecv(ops):
-                w.wait()
-        for sl, rb in recvs:
-            local[sl].copy_(rb)
+            pairs.append((self.rank + 1, own[n - hi_need:], local[lo_need + n:]))
+        if pairs:
+            self.comm.finish(self.comm.start(pairs))
         self.lsim.setElementDensities_padded(local.reshape(-1))
         self._sharded = True
 
@@ -627,22 +556,8 @@ class DistributedMGSolver:
         KE = self.KE_DOUBLES
         mine = torch.empty(count * nyz * KE, dtype=torch.float64, device=self.dev)
         self._chk(self._mg("export_level_ke")(self.lmg, self.T, child.gl + child.extra_lo, count, self._p(mine), self._s()))
-        if self.world == 1:
-            whole = mine
-        elif self.proxy:
-            counts = [(self.part.starts[r + 1] - self.part.starts[r]) >> self.T for r in range(self.world)]
-            whole = torch.cat([mine[:c * nyz * KE] if c <= count else mine.repeat(2)[:c * nyz * KE] for c in counts])
-        else:
-            counts = [(self.part.starts[r + 1] - self.part.starts[r]) >> self.T for r in range(self.world)]
-            staged = dist.get_backend(self.group) == "gloo"
-            where = "cpu" if staged else self.dev
-            # equal-size buffers (slabs may differ by one aligned block; RCCL's all-gather wants one size)
-            most = max(counts) * nyz * KE
-            send = torch.zeros(most, dtype=torch.float64, device=where)
-            send[:mine.numel()].copy_(mine)
-            parts = [torch.empty(most, dtype=torch.float64, device=where) for _ in counts]
-            dist.all_gather(parts, send, group=self.group)
-            whole = torch.cat([b[:c * nyz * KE] for b, c in zip(parts, counts)]).to(self.dev)
+        # (a rank proxy repeats its own block to each rank's size)
+        whole = self.comm.all_gather_slabs(mine, [(n >> self.T) * nyz * KE for n in self.part.layers()])
         self._chk(self._mg("import_level_ke")(self.gmg, self._replicated_level(), self._p(whole), self._s()))
         torch.cuda.current_stream().synchronize()
 
@@ -730,7 +645,7 @@ class DistributedMGSolver:
         self.bT.zero_()
         bv = self.bT.view(-1, g.plane * 3)
         bv[g.xoffn + lo:g.xoffn + hi] = self.b[self.T].view(g.n_planes, -1)[lo:hi]
-        self._allreduce(self.bT)
+        self.comm.all_reduce(self.bT)
         self.xT.zero_()
         self._chk(self._mg("cycle_from_level")(self.gmg, self._replicated_level(), self._p(self.xT), self._p(self.bT), self._nsmooth,
                                                    int(fmg), self._s()))
@@ -786,19 +701,14 @@ class DistributedMGSolver:
         """The whole solve as ONE library call (vfem_mg_pcg_slab): the cycle, the sweeps' exchange logic and the CG loop run in C++;
         Python is entered only for the halo exchanges and the all-reduces (torch.distributed), through two callbacks.  The Python
         driver below (`use_c_driver = False`) is the same algorithm call by call and remains the cross-check."""
-        ct, lib = self._ct, self.lib
-        from . import _lib
-
-        class _DL(ct.Structure):
-            _fields_ = [("n_planes", ct.c_int64), ("plane_nodes", ct.c_int64), ("first_owned", ct.c_int64), ("last_owned", ct.c_int64),
-                        ("xoffn", ct.c_int64), ("gl", ct.c_int32), ("gr", ct.c_int32), ("x", ct.c_void_p), ("b", ct.c_void_p), ("r", ct.c_void_p)]
+        ct, lib = ctypes, self.lib
         if getattr(self, "_cwork", None) is None:
             self._cwork = (torch.zeros_like(self.x[0]), torch.zeros_like(self.x[0]), torch.zeros(8, dtype=torch.float64, device=self.dev))
         d, Ad, sc = self._cwork
         by_ptr = {}
         for t in self.x + self.b + self.r + [self.xT, self.bT, d, Ad, sc, x]:
             by_ptr[t.data_ptr()] = t
-        arr = (_DL * len(self.geom))()
+        arr = (_lib._DL * len(self.geom))()
         for l, g in enumerate(self.geom):
             arr[l].n_planes, arr[l].plane_nodes, arr[l].first_owned, arr[l].last_owned = g.n_planes, g.plane, g.first_owned, g.last_owned
             arr[l].xoffn, arr[l].gl, arr[l].gr = g.xoffn, g.gl, g.gr
@@ -826,7 +736,7 @@ class DistributedMGSolver:
                 base = ptr if ptr in by_ptr else sc.data_ptr()          # (scalars: an address inside the 8-double block)
                 t = by_ptr[base].view(-1)
                 off = (ptr - base) // 8
-                self._allreduce(t[off:off + n])
+                self.comm.all_reduce(t[off:off + n])
                 return 0
             except BaseException as e:
                 failure[0] = e
@@ -904,73 +814,71 @@ class DistributedMGSolver:
 
 
 # ==============================================================================================
-# One evaluation of the train_xdg closure (training/train_xdg.py:282-329) over the slab ranks:
-#   MLP logits of the rank's planes -> constrained sigmoid (mean over the WHOLE field) -> compliance by the distributed
-#   MG-PCG -> sensitivities of the owned elements -> MLP backward on the rank's planes -> one all-reduce of the gradients.
-# The density field crosses ranks once per evaluation (all-gather: the slab solver builds its replicated coarse
-# hierarchy from the whole field); displacements, sensitivities and activations never do.
+# What the design loops over the slab ranks share (distributed_design.DistributedDesignLoop, distributed_xdg.DistributedXdgLoop)
 # ==============================================================================================
-class _ShardedCompliance(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, density_local, trainer):
-        ds = trainer.solver
-        parts = trainer._gather(density_local.detach().to(torch.float64))
-        ds.set_global_densities(parts)
-        f = ds.local_loads()
-        if trainer._u is None or trainer.zero_init:
-            trainer._u = torch.zeros_like(f)
-        trainer._u = ds.pcg(trainer._u, f, trainer.cg_iter, trainer.tol, 1, 2, True)
-        # as in the reference's autograd node the value is 2 J but the gradient is that of J (fem.py:122-126)
-        ctx.save_for_backward(ds.compliance_gradient(trainer._u).to(torch.float32))
-        return density_local.new_tensor(2.0 * ds.compliance(f, trainer._u))
+class SlabLoop:
+    """Refuses what has no slab form, builds the solver, and solves as fem.DesignLoop's objective does: one solve from zero at the
+    uniform volume fraction with FIRST_TOL (`_first_solve`), every later one warm-started with SOLVER.  Degree 1, 3-D, multigrid."""
 
-    @staticmethod
-    def backward(ctx, grad_output):
-        (g,) = ctx.saved_tensors
-        return g * grad_output, None
+    SOLVER = fem.DesignLoop.SOLVER
+    CG_ITER = 100            # MultigridComplianceObjective's default, which the one-GPU drivers keep
+    FIRST_TOL = 1e-5         # MultigridComplianceObjective's constructor solves once at its default tolerance, before SOLVER is set
+
+    def __init__(self, material, bcs, order, corners, grid, simp_exponent, mg_levels, use_multigrid=True, dist_levels=None, group=None):
+        name = type(self).__name__
+        if len(grid) != 3 or len(order) != 3:
+            raise RuntimeError("%s: 3-D grids only (got a %d-D grid)" % (name, len(grid)))
+        if list(order) != [1, 1, 1]:
+            raise RuntimeError("%s: degree [1, 1, 1] only (got %s)" % (name, list(order)))
+        if not use_multigrid or int(mg_levels) < 1:
+            raise RuntimeError("%s: the slab solve is multigrid PCG; the direct objective (no multigrid) has no "
+                               "distributed form" % name)
+        corners = [np.asarray(c, dtype=np.float64) for c in corners]
+        self.ds = ds = DistributedMGSolver(grid, corners[0], corners[1], bcs, material, int(mg_levels), dist_levels=dist_levels,
+                                           E0=1.0, Emin=1e-4, gamma=float(simp_exponent), group=group)
+        self.comm, self.world, self.rank, self.ne, self.dev = ds.comm, ds.world, ds.rank, ds.ne, ds.dev
+        self.layer = self.ne[1] * self.ne[2]
+
+    def _first_solve(self, phys):
+        self._f = self.ds.local_loads()
+        self._u = torch.zeros_like(self._f)
+        self._set_densities(phys)
+        self._solve(self.FIRST_TOL)
+
+    def _set_densities(self, owned):
+        self.ds.set_local_densities(owned)
+
+    def _solve(self, tol):
+        s = self.SOLVER
+        if s["zeroInit"]:
+            self._u.zero_()
+        self._u = self.ds.pcg(self._u, self._f, self.CG_ITER, tol, s["mgIterations"], s["mgSmoothingIterations"], s["fullMultigrid"])
 
 
-class DistributedDensityTrainer:
-    """density = constrained_sigmoid(mlp(grid)) sharded by x-planes; loss = compliance of the distributed solve"""
+# ==============================================================================================
+# Rank processes of the training drivers (--gpus N without a launcher)
+# ==============================================================================================
+def _rank_entry(rank, world, port, entry, argv):
+    """a rank process started by `launch_ranks` (fresh interpreter, nothing has touched the GPU yet)"""
+    os.environ.update({'RANK': str(rank), 'LOCAL_RANK': str(rank), 'WORLD_SIZE': str(world), 'MASTER_ADDR': '127.0.0.1',
+                       'MASTER_PORT': str(port), 'HSA_ENABLE_IPC_MODE_LEGACY': os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY', '0')})
+    entry(argv)
 
-    def __init__(self, solver, net, max_volume, tol=1e-4, cg_iter=100, zero_init=False):
-        self.solver, self.net, self.max_volume = solver, net, float(max_volume)
-        self.tol, self.cg_iter, self.zero_init = tol, cg_iter, zero_init
-        self.first, self.count = solver.owned_element_range()
-        net.set_grid(solver.ne, voxel_range=(self.first, self.count))
-        self._u = None
-        self.world = dist.get_world_size() if dist.is_initialized() else 1
 
-    def _reduce(self, t, op):
-        if self.world == 1:
-            return t
-        if dist.get_backend() == "gloo":
-            h = t.detach().cpu()
-            dist.all_reduce(h, op=op)
-            return h.to(t.device)
-        t = t.detach().clone()
-        dist.all_reduce(t, op=op)
-        return t
-
-    def _gather(self, local):
-        if self.world == 1:
-            return local
-        counts = [None] * self.world
-        dist.all_gather_object(counts, int(local.numel()))
-        m = max(counts)                                   # equal-size buffers (slabs differ by at most one aligned block)
-        gloo = dist.get_backend() == "gloo"
-        mine = torch.zeros(m, dtype=local.dtype, device="cpu" if gloo else local.device)
-        mine[:local.numel()] = local.cpu() if gloo else local
-        bufs = [torch.empty_like(mine) for _ in counts]
-        dist.all_gather(bufs, mine)
-        return torch.cat([b[:c] for b, c in zip(bufs, counts)]).to(local.device)
-
-    def loss(self):
-        """compliance (2 J) of the constrained density predicted by the network; call .backward() on it"""
-        from . import fem
-        logits = self.net.forward_grid()
-        density = fem.sigmoid_with_constrained_mean(
-            logits, torch.tensor(self.max_volume, device=logits.device),
-            allsum=lambda t: self._reduce(t, dist.ReduceOp.SUM), allmax=lambda t: self._reduce(t, dist.ReduceOp.MAX))
-        self.last_density = density.detach()
-        return _ShardedCompliance.apply(density, self)
+def launch_ranks(world, entry, argv):
+    """start `world` rank processes that each run entry(argv) with the environment of torch.distributed.run (spawn: fresh
+    children; this parent never initialises the GPU) and wait for them; SystemExit with the worst exit code if one failed"""
+    import socket
+    import torch.multiprocessing as mp
+    with socket.socket() as sk:
+        sk.bind(('127.0.0.1', 0))
+        port = sk.getsockname()[1]
+    procs = [mp.get_context('spawn').Process(target=_rank_entry, args=(r, world, port, entry, argv)) for r in range(world)]
+    for pr in procs:
+        pr.start()
+    code = 0
+    for pr in procs:
+        pr.join()
+        code = max(code, abs(pr.exitcode or 0))
+    if code:
+        raise SystemExit('a rank process failed (exit code {})'.format(code))

@@ -21,47 +21,28 @@ import time
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
 from . import _lib
-from .distributed import DistributedMGSolver
+from .distributed import SlabLoop
+from .pyVoxelFEM import _ptr, _stream
 
 
-class DistributedDesignLoop:
+class DistributedDesignLoop(SlabLoop):
     """fem.DesignLoop on the slab ranks (one instance per rank, all ranks call every method in the same order).
 
     The constructor takes DesignLoop's arguments plus `dist_levels` (distributed multigrid levels, default: the solver's automatic
     choice) and `group` (torch.distributed group).  `radius` (smoothing filter) and `beta` (projection filter) default to 1 and 1
     as in DesignLoop's filter chain and may be changed before `seed`."""
 
-    SOLVER = {"tol": 1e-4, "mgIterations": 1, "fullMultigrid": True, "zeroInit": False, "mgSmoothingIterations": 2}
-    CG_ITER = 100            # MultigridComplianceObjective's default, which DesignLoop keeps
-    FIRST_TOL = 1e-5         # MultigridComplianceObjective's constructor solves once at its default tolerance, before SOLVER is set
-
     def __init__(self, material, bcs, order, corners, grid, simp_exponent, volume_fraction, mg_levels, use_multigrid=True,
                  dist_levels=None, group=None):
-        if len(grid) != 3 or len(order) != 3:
-            raise RuntimeError("DistributedDesignLoop: 3-D grids only (got a %d-D grid)" % len(grid))
-        if list(order) != [1, 1, 1]:
-            raise RuntimeError("DistributedDesignLoop: degree [1, 1, 1] only (got %s)" % list(order))
-        if not use_multigrid or int(mg_levels) < 1:
-            raise RuntimeError("DistributedDesignLoop: the slab solve is multigrid PCG; the direct objective (no multigrid) has no "
-                               "distributed form")
-        corners = [np.asarray(c, dtype=np.float64) for c in corners]
+        super().__init__(material, bcs, order, corners, grid, simp_exponent, mg_levels, use_multigrid, dist_levels, group)
         self.order = list(order)
-        self.group = group
         self.v = float(volume_fraction)
         self.radius, self.beta = 1, 1.0
-        self.ds = DistributedMGSolver(grid, corners[0], corners[1], bcs, material, int(mg_levels), dist_levels=dist_levels,
-                                      E0=1.0, Emin=1e-4, gamma=float(simp_exponent), group=group)
-        ds = self.ds
-        self.world, self.rank = ds.world, ds.rank
-        self.ne = ds.ne
-        self.layer = self.ne[1] * self.ne[2]
         self.N = self.ne[0] * self.layer
-        self.x0, self.x1 = ds.part.x0, ds.part.x1
+        self.x0, self.x1 = self.ds.part.x0, self.ds.part.x1
         self.own = self.x1 - self.x0
-        self.dev = ds.dev
         self.lib = _lib.load()
         self.history = []
         self.adaptive_filtering = None
@@ -70,21 +51,16 @@ class DistributedDesignLoop:
         self.timers = {"solve": 0.0, "update": 0.0, "comm": 0.0}
         self._lmin, self._lmax = 1.0, 2.0
         self._check_radius()
-        # the objective's constructor: densities at the volume fraction, one solve from zero
         self._phys = torch.full((self.own * self.layer,), self.v, dtype=torch.float64, device=self.dev)
         self._vars = None
-        self._f = ds.local_loads()
-        self._u = torch.zeros_like(self._f)
-        self._set_densities(self._phys)
-        self._solve(self.FIRST_TOL)
+        self._first_solve(self._phys)
 
     # ---- geometry -----------------------------------------------------------------------------------
     def _check_radius(self):
         r = int(self.radius)
         if r < 0:
             raise RuntimeError("DistributedDesignLoop: negative filter radius %d" % r)
-        starts = self.ds.part.starts
-        thinnest = min(starts[k + 1] - starts[k] for k in range(self.world))
+        thinnest = min(self.ds.part.layers())
         if self.world > 1 and r > thinnest:
             raise RuntimeError("DistributedDesignLoop: filter radius %d exceeds the %d owned element layers of the thinnest slab; "
                                "use fewer ranks or a smaller radius" % (r, thinnest))
@@ -97,36 +73,23 @@ class DistributedDesignLoop:
     # ---- element-layer exchange ------------------------------------------------------------------------
     def _exchange(self, fields):
         """fill the ghost layers of the extended arrays `fields` (each [(gl + own + gr) * layer]) from the neighbours' owned layers:
-        one message per neighbour and direction for all fields together (batched isend / irecv as HaloExchanger.start; gloo stages
-        through the host, nccl sends device buffers)"""
+        one message per neighbour and direction for all fields together"""
         gl, gr = self._ghosts()
         if self.world == 1 or (gl == 0 and gr == 0):
             return
         clock = time.perf_counter()
         views = [f.view(-1, self.layer) for f in fields]
-        staged = views[0].is_cuda and dist.get_backend(self.group) == "gloo"
-        ops, recvs = [], []
-
-        def add(send_first, count, recv_first, peer):
-            sb = torch.cat([v[send_first:send_first + count] for v in views])
-            if staged:
-                sb = sb.cpu()
-            rb = torch.empty_like(sb)
-            ops.append(dist.P2POp(dist.isend, sb, peer, self.group))
-            ops.append(dist.P2POp(dist.irecv, rb, peer, self.group))
-            recvs.append((recv_first, count, rb))
-
-        if gl:
-            add(gl, gl, 0, self.rank - 1)
-        if gr:
-            add(gl + self.own - gr, gr, gl + self.own, self.rank + 1)
-        for w in dist.batch_isend_irecv(ops):
-            w.wait()
-        for first, count, rb in recvs:
-            rb = rb.to(self.dev).view(len(views), count, self.layer)
-            for v, part in zip(views, rb):
+        pairs, slots = [], []
+        for peer, send_first, count, recv_first in ((self.rank - 1, gl, gl, 0), (self.rank + 1, gl + self.own - gr, gr, gl + self.own)):
+            if count:
+                sb = torch.cat([v[send_first:send_first + count] for v in views])
+                pairs.append((peer, sb, torch.empty_like(sb)))
+                slots.append((recv_first, count))
+        self.comm.finish(self.comm.start(pairs))
+        for (_, _, rb), (first, count) in zip(pairs, slots):
+            for v, part in zip(views, rb.view(len(views), count, self.layer)):
                 v[first:first + count].copy_(part)
-        self.messages += len(recvs)
+        self.messages += len(pairs)
         self.timers["comm"] += time.perf_counter() - clock
 
     def _extend(self, owned):
@@ -139,42 +102,34 @@ class DistributedDesignLoop:
         if self.world == 1:
             return value
         clock = time.perf_counter()
-        t = torch.tensor([value], dtype=torch.float64, device="cpu" if dist.get_backend(self.group) == "gloo" else self.dev)
-        dist.all_reduce(t, group=self.group)
+        t = self.comm.all_reduce(torch.tensor([value], dtype=torch.float64))
         self.timers["comm"] += time.perf_counter() - clock
         return float(t[0])
 
     # ---- device kernels ----------------------------------------------------------------------------
-    def _s(self):
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-    @staticmethod
-    def _p(t):
-        return ctypes.c_void_p(t.data_ptr())
-
     def _box(self, ext, transpose):
         """slab box filter of the extended array `ext` (owned + ghost layers), owned layers out"""
         gl, gr = self._ghosts()
         out = torch.empty((self.own * self.layer,), dtype=torch.float64, device=self.dev)
         n = (ctypes.c_int64 * 3)(gl + self.own + gr, self.ne[1], self.ne[2])
-        _lib.check(self.lib.vfem_box_filter_slab(n, self.x0 - gl, self.ne[0], gl, self.own, int(self.radius), self._p(ext),
-                                                 self._p(out), int(transpose), self._s()))
+        _lib.check(self.lib.vfem_box_filter_slab(n, self.x0 - gl, self.ne[0], gl, self.own, int(self.radius), _ptr(ext),
+                                                 _ptr(out), int(transpose), _stream()))
         return out
 
     def _projection(self, x):
         out = torch.empty_like(x)
-        _lib.check(self.lib.vfem_projection(x.numel(), float(self.beta), self._p(x), self._p(out), self._s()))
+        _lib.check(self.lib.vfem_projection(x.numel(), float(self.beta), _ptr(x), _ptr(out), _stream()))
         return out
 
     def _projection_backprop(self, g, x):
         out = torch.empty_like(g)
-        _lib.check(self.lib.vfem_projection_backprop(g.numel(), float(self.beta), self._p(g), self._p(x), self._p(out), self._s()))
+        _lib.check(self.lib.vfem_projection_backprop(g.numel(), float(self.beta), _ptr(g), _ptr(x), _ptr(out), _stream()))
         return out
 
     def _sum(self, x):
         """global sum of the owned values `x`: local device reduction, one scalar all-reduce"""
         m = ctypes.c_double(0.0)
-        _lib.check(self.lib.vfem_mean(x.numel(), self._p(x), ctypes.byref(m), self._s()))
+        _lib.check(self.lib.vfem_mean(x.numel(), _ptr(x), ctypes.byref(m), _stream()))
         return self._allreduce(m.value * x.numel())
 
     def _volume_constraint(self, phys):
@@ -184,17 +139,14 @@ class DistributedDesignLoop:
     # ---- problem -----------------------------------------------------------------------------------
     def _set_densities(self, phys):
         clock = time.perf_counter()
-        self.ds.set_local_densities(phys)
+        super()._set_densities(phys)
         self.messages += (self.rank > 0) + (self.rank < self.world - 1)
         self.timers["comm"] += time.perf_counter() - clock
 
     def _solve(self, tol):
         torch.cuda.synchronize()
         clock = time.perf_counter()
-        s = self.SOLVER
-        if s["zeroInit"]:
-            self._u.zero_()
-        self._u = self.ds.pcg(self._u, self._f, self.CG_ITER, tol, s["mgIterations"], s["mgSmoothingIterations"], s["fullMultigrid"])
+        super()._solve(tol)
         self.pcg_iterations.append(self.ds.last_iterations)
         torch.cuda.synchronize()
         self.timers["solve"] += time.perf_counter() - clock
@@ -249,18 +201,8 @@ class DistributedDesignLoop:
 
     def gather_densities(self, dst=0):
         """physical densities of the whole grid as a numpy array [nx * ny * nz] on rank `dst` (None on the others)"""
-        if self.world == 1:
-            return self._phys.cpu().numpy()
-        starts = self.ds.part.starts
-        counts = [(starts[k + 1] - starts[k]) * self.layer for k in range(self.world)]
-        where = "cpu" if dist.get_backend(self.group) == "gloo" else self.dev
-        mine = torch.zeros(max(counts), dtype=torch.float64, device=where)       # equal-size buffers
-        mine[:self._phys.numel()].copy_(self._phys)
-        bufs = [torch.empty_like(mine) for _ in counts] if self.rank == dst else None
-        dist.gather(mine, bufs, dst=dst, group=self.group)
-        if self.rank != dst:
-            return None
-        return torch.cat([b[:c] for b, c in zip(bufs, counts)]).cpu().numpy()
+        whole = self.comm.gather_slabs(self._phys, [n * self.layer for n in self.ds.part.layers()], dst)
+        return None if whole is None else whole.cpu().numpy()
 
     # ---- optimality criterion ----------------------------------------------------------------------
     def _gradients(self):
@@ -288,8 +230,8 @@ class DistributedDesignLoop:
         probes = [0]
 
         def stepped(lam):
-            _lib.check(self.lib.vfem_oc_candidate(x0.numel(), self._p(x0), self._p(dJe), self._p(dce), float(lam), float(m),
-                                                  self._p(cand), self._s()))
+            _lib.check(self.lib.vfem_oc_candidate(x0.numel(), _ptr(x0), _ptr(dJe), _ptr(dce), float(lam), float(m),
+                                                  _ptr(cand), _stream()))
             return cand
 
         def ceval(lam):

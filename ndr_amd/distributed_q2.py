@@ -23,7 +23,9 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .distributed import DistributedMGSolver, HaloExchanger, SlabPartition
+from . import _lib
+from .distributed import DistributedMGSolver, LevelGeom
+from .slab_comm import MAX
 
 P = 2            # polynomial degree
 G = 2            # ghost element layers per neighbour
@@ -133,38 +135,17 @@ def slab_masks_and_loads(bbmin, bbmax, ne, bc_path, geom, T, device):
     return masks, loads.reshape(-1, 3), masks[T]
 
 
-class _LevelGeomQ2:
-    """local grid of one rank on level l; planes are node planes of that level (2 per element layer)"""
-
-    def __init__(self, part, l, Ld, ne0):
-        s = 2 ** l
-        has_l, has_r = part.rank > 0, part.rank < part.world - 1
-        self.l = l
-        self.X0, self.X1 = part.x0 // s, part.x1 // s
-        self.gl, self.gr = (G if has_l else 0), (G if has_r else 0)          # ghost ELEMENT layers
-        self.nx = self.X1 - self.X0 + self.gl + self.gr
-        self.ny, self.nz = ne0[1] // s, ne0[2] // s
-        self.n_planes = P * self.nx + 1
-        self.plane = (P * self.ny + 1) * (P * self.nz + 1)
-        self.halo_width = P * G
-        self.first_owned = P * self.gl
-        self.last_owned = self.first_owned + P * (self.X1 - self.X0)
-        self.xoffe = self.X0 - self.gl                                       # global element layer of local layer 0
-        self.xoffn = P * self.xoffe                                          # global node plane of local plane 0
-        pad = G * (2 ** (Ld - l) - 1) if l <= Ld else 0
-        self.extra_lo, self.extra_hi = (pad if has_l else 0), (pad if has_r else 0)
-        self.xshift = -P * self.gl if l > 0 else 0                           # fine local plane = 2 * local plane + xshift
-        self.xparity = self.xoffe & 1
-        self.rank, self.world = part.rank, part.world
-
-    def reduction_weight_planes(self):
-        return self.first_owned, self.last_owned + (1 if self.rank == self.world - 1 else 0)
+def _LevelGeomQ2(part, l, Ld, ne0):
+    return LevelGeom(part, l, Ld, ne0, degree=P, ghost=G)
 
 
 class DistributedMGSolverQ2(DistributedMGSolver):
-    """Slab-decomposed multigrid PCG for TensorProductSimulator<2,2,2> (one instance per rank); the cycles, the PCG recurrence
-    and the reductions are the base class's."""
+    """Slab-decomposed multigrid PCG for TensorProductSimulator<2,2,2> (one instance per rank); the constructor's shared steps, the
+    cycles, the PCG recurrence and the reductions are the base class's.  As a rank proxy (`proxy = (world, rank)`, tools/rank_proxy.py
+    q2 ...) the replicated level's mask is this rank's planes of it plus a clamped face x = 0 (values are meaningless, work, launches
+    and memory are the real rank's)."""
 
+    DEGREE, GHOST = P, G
     C_DRIVER_AVAILABLE = False     # the degree-2 cycle (27 colours in three groups, four-plane halos) is driven from Python
     _MG_PREFIX = "vfem_gmg_"
     KE_DOUBLES = 81 * 81
@@ -173,53 +154,18 @@ class DistributedMGSolverQ2(DistributedMGSolver):
     MIN_SHARDED_T = 1
     ALWAYS_ASSEMBLE = True
 
+    MIN_LAYERS = 2 * G             # deepest distributed level: every rank still owns >= 2 G element layers there
     MAX_AUTO_DIST_LEVELS = 2       # the element arrays of level l keep G (2^(Ld-l) - 1) padding layers per neighbour: 81 x 81
                                    # matrices on level 1, so the automatic choice stops at two coarsenings
 
-    def __init__(self, ne, bbmin, bbmax, bc_path, material_path, num_levels, dist_levels=None, E0=1.0, Emin=1e-4,
-                 gamma=3.0, group=None, proxy=None):
-        """proxy = (world, rank): the slab of ONE rank of `world` built in a single process (tools/rank_proxy.py q2 ...): messages
-        become device copies of the same bytes, reductions stay local, the replicated level's mask is this rank's planes of it plus a
-        clamped face x = 0 (values are meaningless, work, launches and memory are the real rank's)."""
-        from . import _lib
+    def _create_simulators(self, bbmin, bbmax, local_box, bc_path, material):
         from . import pyVoxelFEM as pv
-        self._ct, self._lib_mod, self._pv = ctypes, _lib, pv
-        self.lib = _lib.load()
-        self.group = group
-        self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        self.proxy = proxy is not None
-        if self.proxy:
-            self.world, self.rank = int(proxy[0]), int(proxy[1])
-        self.ne = tuple(int(v) for v in ne)
-        self.L = int(num_levels)
-        if dist_levels is None:
-            # deepest distributed level: every rank still owns >= 2 G element layers there
-            dist_levels = 0
-            while (dist_levels + 1 < self.L and dist_levels < self.MAX_AUTO_DIST_LEVELS
-                   and self.ne[0] % (self.world * 2 ** (dist_levels + 2)) == 0
-                   and self.ne[0] // (self.world * 2 ** (dist_levels + 1)) >= 2 * G):
-                dist_levels += 1
-        self.Ld = int(dist_levels)
-        if self.Ld + 1 > self.L:
-            raise RuntimeError("need at least one replicated level below the distributed ones")
-        self.T = self.Ld + 1
-        self.part = SlabPartition(self.ne, self.world, self.rank, align=2 ** (self.Ld + 1))
-        if self.world > 1 and (self.part.x1 - self.part.x0) >> self.Ld < G:
-            raise RuntimeError("slab thinner than the ghost layers on the deepest distributed level")
-        self.geom = [_LevelGeomQ2(self.part, l, self.Ld, self.ne) for l in range(self.T + 1)]
-        self.dev = torch.device("cuda", torch.cuda.current_device())
-
         # No object of the size of the whole fine grid exists anywhere: boundary conditions are evaluated for this rank's planes
         # (plus the margin the coarsened masks of its deeper levels depend on), and the replicated hierarchy is created on the
         # grid of level T itself, its level-0 element matrices imported from the ranks (vfem_gmg_import_level_ke).
-        bbmin, bbmax = np.asarray(bbmin, float), np.asarray(bbmax, float)
         masks, self._loads_local, maskT = slab_masks_and_loads(bbmin, bbmax, self.ne, bc_path, self.geom, self.T, self.dev)
-        self._masks = masks
         neT = [n >> self.T for n in self.ne]
-        self.gsim = pv.TensorProductSimulator2_2_2([bbmin, bbmax], neT)
-        self.gsim.readMaterial(material_path)
-        self.gsim.E_0, self.gsim.E_min, self.gsim.gamma = E0, Emin, gamma
+        self.gsim = material(pv.TensorProductSimulator2_2_2([bbmin, bbmax], neT))
         gT = self.geom[self.T]
         lo_p, hi_p = gT.reduction_weight_planes()
         mine = np.ascontiguousarray(maskT.reshape(gT.n_planes, -1)[lo_p:hi_p])
@@ -229,7 +175,7 @@ class DistributedMGSolverQ2(DistributedMGSolver):
             whole[0] = 7
         elif self.world > 1:
             parts = [None] * self.world
-            dist.all_gather_object(parts, mine, group=group)
+            dist.all_gather_object(parts, mine, group=self.group)
             whole = np.concatenate(parts, axis=0)
         else:
             whole = mine
@@ -238,45 +184,13 @@ class DistributedMGSolverQ2(DistributedMGSolver):
             raise RuntimeError("assembled level-%d mask has %d nodes, expected %d" % (self.T, whole.size, self.gsim.numNodes()))
         self.gsim._mask = np.stack([(whole >> c) & 1 for c in range(3)], axis=1).astype(bool)
         self.gsim._push_dirichlet()
-        h = ctypes.c_void_p()
-        _lib.check(self.lib.vfem_gmg_create(ctypes.byref(h), self.gsim._h, self.L - self.T))
-        self.gmg = h
-
+        self.gmg = ctypes.c_void_p()
+        _lib.check(self.lib.vfem_gmg_create(ctypes.byref(self.gmg), self.gsim._h, self.L - self.T))
         # local slab simulator: owned + ghost element layers as its node grid, padding layers in the density array only
         g0 = self.geom[0]
-        hx = (bbmax[0] - bbmin[0]) / self.ne[0]
-        lo, hi = bbmin.copy(), bbmax.copy()
-        lo[0], hi[0] = bbmin[0] + g0.xoffe * hx, bbmin[0] + (g0.xoffe + g0.nx) * hx
-        self.lsim = pv.TensorProductSimulator2_2_2([lo, hi], [g0.nx, self.ne[1], self.ne[2]],
-                                                   _element_padding=(g0.extra_lo, g0.extra_hi))
-        self.lsim.readMaterial(material_path)
-        self.lsim.E_0, self.lsim.E_min, self.lsim.gamma = E0, Emin, gamma
-        m0 = masks[0]
-        self.lsim._mask = np.stack([(m0 >> c) & 1 for c in range(3)], axis=1).astype(bool)
-        self.lsim._dvals = np.zeros((m0.size, 3))
-        self.lsim._push_dirichlet()
-
-        class _SL(ctypes.Structure):
-            _fields_ = [("nx", ctypes.c_int64), ("elem_extra_lo", ctypes.c_int64), ("elem_extra_hi", ctypes.c_int64),
-                        ("xshift", ctypes.c_int64), ("xparity", ctypes.c_int32)]
-        arr = (_SL * len(self.geom))()
-        for l, g in enumerate(self.geom):
-            arr[l].nx, arr[l].elem_extra_lo, arr[l].elem_extra_hi = g.nx, g.extra_lo, g.extra_hi
-            arr[l].xshift, arr[l].xparity = g.xshift, g.xparity
-        mptrs = (ctypes.c_void_p * len(masks))(*[m.ctypes.data_as(ctypes.c_void_p).value for m in masks])
-        h2 = ctypes.c_void_p()
-        _lib.check(self.lib.vfem_gmg_create_slab(ctypes.byref(h2), self.lsim._h, len(self.geom), arr, mptrs))
-        self.lmg = h2
-        self.halos = [HaloExchanger(g, group, self.proxy) for g in self.geom]
-        z = lambda g: torch.zeros((g.n_planes * g.plane, 3), dtype=torch.float64, device=self.dev)
-        self.x = [z(g) for g in self.geom]
-        self.b = [z(g) for g in self.geom]
-        self.r = [z(g) for g in self.geom[:-1]]
-        gT = int(self.lib.vfem_gmg_level_num_nodes(self.gmg, 0))
-        self.xT = torch.zeros((gT, 3), dtype=torch.float64, device=self.dev)
-        self.bT = torch.zeros((gT, 3), dtype=torch.float64, device=self.dev)
-        self.symmetric_gs = True
-        self.last_iterations, self.last_relative_residual = 0, 0.0
+        self.lsim = material(pv.TensorProductSimulator2_2_2(local_box, [g0.nx, self.ne[1], self.ne[2]],
+                                                            _element_padding=(g0.extra_lo, g0.extra_hi)))
+        return masks
 
     def _export_child_level(self):
         return self.T - 1
@@ -317,12 +231,7 @@ def bench_pcg_q2(ne, levels, tol=1e-4):
     t0 = time.perf_counter()
     u = ds.pcg(torch.zeros_like(f), f, 100, tol, 1, 2, True)
     torch.cuda.synchronize()
-    dt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
-    if dist.is_initialized():
-        if dist.get_backend() != "gloo":
-            dt = dt.cuda()
-        dist.all_reduce(dt, op=dist.ReduceOp.MAX)
-    dt = float(dt.item())
+    dt = float(ds.comm.all_reduce(torch.tensor([time.perf_counter() - t0], dtype=torch.float64), MAX).item())
     return {"grid": "%dx%dx%d" % tuple(ne), "degree": 2, "nodes": int(np.prod([P * n + 1 for n in ne])), "levels": levels,
             "distributed_levels": ds.Ld + 1, "iterations": ds.last_iterations, "seconds": dt,
             "iterations_per_s": ds.last_iterations / dt, "relative_residual": ds.last_relative_residual,

@@ -15,12 +15,11 @@ voxel_range=...)`) and holds the same parameters.  One step:
 The loss is the whole field's on every rank.  Degree 1, 3-D, multigrid only."""
 import time
 
-import numpy as np
 import torch
-import torch.distributed as dist
 
 from . import fem
-from .distributed import DistributedDensityTrainer, DistributedMGSolver
+from .distributed import SlabLoop
+from .slab_comm import MAX, SUM
 
 
 class _SlabCompliance(torch.autograd.Function):
@@ -40,7 +39,7 @@ class _SlabCompliance(torch.autograd.Function):
         return g * grad_output, None
 
 
-class DistributedXdgLoop:
+class DistributedXdgLoop(SlabLoop):
     """train_xdg's loop on the slab ranks (one instance per rank; all ranks call every method in the same order).
 
     Solver as the one-GPU driver sets it up (E0 = 1, Emin = 1e-4, SIMP exponent 3, fem.DesignLoop.SOLVER, 100 PCG iterations at
@@ -52,76 +51,44 @@ class DistributedXdgLoop:
     (T >= MIN_SHARDED_T), otherwise the gather of the whole field + set_global_densities.  `steps` keeps, per step, the loss, the
     PCG iterations and the wall time of the five parts (TIMERS)."""
 
-    SOLVER = fem.DesignLoop.SOLVER
-    CG_ITER = 100            # MultigridComplianceObjective's default, which train_xdg keeps
-    FIRST_TOL = 1e-5         # MultigridComplianceObjective's constructor solves once at its default tolerance, before SOLVER is set
     TIMERS = ("forward", "satisfier", "solve", "backward", "adam")
 
     def __init__(self, material, bcs, order, corners, grid, volume_fraction, mg_levels, vcs="constrained_sigmoid", dist_levels=None,
                  log=None):
-        if len(grid) != 3 or len(order) != 3:
-            raise RuntimeError("DistributedXdgLoop: 3-D grids only (got a %d-D grid)" % len(grid))
-        if list(order) != [1, 1, 1]:
-            raise RuntimeError("DistributedXdgLoop: degree [1, 1, 1] only (got %s)" % list(order))
-        if int(mg_levels) < 1:
-            raise RuntimeError("DistributedXdgLoop: the slab solve is multigrid PCG; the direct objective (no multigrid) has no "
-                               "distributed form")
-        self.hard = fem.type_of_volume_constaint_satisfier(vcs)
+        self.hard = fem.type_of_volume_constaint_satisfier(vcs)      # (an unknown satisfier is refused before the solver is built)
         self.vcs = vcs
+        super().__init__(material, bcs, order, corners, grid, 3.0, mg_levels, dist_levels=dist_levels)   # train_xdg forces the SIMP exponent to 3
         self.v = float(volume_fraction)
-        corners = [np.asarray(c, dtype=np.float64) for c in corners]
-        # train_xdg forces the SIMP exponent to 3 (and E0 = 1, Emin = 1e-4)
-        self.ds = DistributedMGSolver(grid, corners[0], corners[1], bcs, material, int(mg_levels), dist_levels=dist_levels,
-                                      E0=1.0, Emin=1e-4, gamma=3.0)
         ds = self.ds
-        self.world, self.rank, self.ne = ds.world, ds.rank, ds.ne
-        self.dev = ds.dev
         self.first, self.count = ds.owned_element_range()
         self.sharded = ds.T >= ds.MIN_SHARDED_T
         if log is not None and self.rank == 0:
             log.write("Densities to the solver: {} ({} ranks, {} distributed levels)\n".format(
                 "sharded (set_local_densities)" if self.sharded else "gathered (all-gather + set_global_densities)",
                 self.world, ds.Ld + 1))
-        self.net, self.trainer = None, None
+        self.net = None
         self.steps = []
         self._max_volume = torch.tensor(self.v, device=self.dev)
-        # the objective's constructor: densities at the volume fraction, one solve from zero
-        self._f = ds.local_loads()
-        self._u = torch.zeros_like(self._f)
-        self._iterations = 0
-        self._set_densities(torch.full((self.count,), self.v, dtype=torch.float64, device=self.dev))
-        self._solve(self.FIRST_TOL)
+        self._first_solve(torch.full((self.count,), self.v, dtype=torch.float64, device=self.dev))
 
     # ---- collectives --------------------------------------------------------------------------------
     def _allsum(self, t):
-        return self.trainer._reduce(t, dist.ReduceOp.SUM)
+        return self.comm.all_reduce(t.detach().clone(), SUM)
 
     def _allmax(self, t):
-        return self.trainer._reduce(t, dist.ReduceOp.MAX)
-
-    def _gloo(self):
-        return self.world > 1 and dist.get_backend() == "gloo"
+        return self.comm.all_reduce(t.detach().clone(), MAX)
 
     def broadcast_parameters(self, src=0):
         """parameters and B of rank `src` to every rank (at the start and after a checkpoint is loaded)"""
-        if self.world == 1:
-            return
-        with torch.no_grad():
-            for t in [self.net.B] + list(self.net.parameters()):
-                if self._gloo():
-                    h = t.detach().cpu()
-                    dist.broadcast(h, src)
-                    t.copy_(h)
-                else:
-                    dist.broadcast(t.data, src)
+        for t in [self.net.B] + list(self.net.parameters()):
+            self.comm.broadcast(t.data, src)
 
     def check_parameters(self):
         """raise unless every rank holds the same parameters: one all-reduce (MAX) of [sum, sum of squares] and their negatives"""
         with torch.no_grad():
             s = sum(float(p.double().sum()) for p in self.net.parameters())
             q = sum(float(p.double().square().sum()) for p in self.net.parameters())
-        mine = torch.tensor([s, q, -s, -q], dtype=torch.float64, device=self.dev)
-        agreed = self.trainer._reduce(mine, dist.ReduceOp.MAX) if self.world > 1 else mine
+        agreed = self.comm.all_reduce(torch.tensor([s, q, -s, -q], dtype=torch.float64, device=self.dev), MAX)
         most, least = agreed[:2].tolist(), (-agreed[2:]).tolist()
         if most != least:
             raise RuntimeError("DistributedXdgLoop: the ranks' parameters differ (checksums: max %r, min %r)" % (most, least))
@@ -129,71 +96,57 @@ class DistributedXdgLoop:
     # ---- network ------------------------------------------------------------------------------------
     def attach(self, net):
         self.net = net
-        self.trainer = DistributedDensityTrainer(self.ds, net, self.v, tol=self.SOLVER["tol"], cg_iter=self.CG_ITER)
         net.set_grid(self.ne, voxel_range=(self.first, self.count))
         self.broadcast_parameters()
         return self
 
     # ---- solve --------------------------------------------------------------------------------------
-    def _gather(self, owned):
-        if self.world == 1:
-            return owned
-        starts = self.ds.part.starts
-        layer = self.ne[1] * self.ne[2]
-        counts = [(starts[k + 1] - starts[k]) * layer for k in range(self.world)]
-        where = "cpu" if self._gloo() else self.dev
-        mine = torch.zeros(max(counts), dtype=owned.dtype, device=where)       # equal-size buffers
-        mine[:owned.numel()].copy_(owned)
-        bufs = [torch.empty_like(mine) for _ in counts]
-        dist.all_gather(bufs, mine)
-        return torch.cat([b[:c] for b, c in zip(bufs, counts)]).to(self.dev)
-
     def _set_densities(self, owned):
         if self.sharded:
             self.ds.set_local_densities(owned)
         else:
-            self.ds.set_global_densities(self._gather(owned))
-
-    def _solve(self, tol):
-        s = self.SOLVER
-        if s["zeroInit"]:
-            self._u.zero_()
-        self._u = self.ds.pcg(self._u, self._f, self.CG_ITER, tol, s["mgIterations"], s["mgSmoothingIterations"], s["fullMultigrid"])
-        self._iterations = self.ds.last_iterations
+            self.ds.set_global_densities(self.comm.all_gather_slabs(owned, [n * self.layer for n in self.ds.part.layers()]))
 
     # ---- one step -----------------------------------------------------------------------------------
-    def step(self, lr):
-        """one step of train_xdg's loop; returns the loss (the whole field's, the same on every rank)"""
-        net, t = self.net, dict.fromkeys(self.TIMERS, 0.0)
-
-        def lap(name, clock):
-            torch.cuda.synchronize()
-            now = time.perf_counter()
-            t[name] += now - clock
-            return now
-
-        torch.cuda.synchronize()
-        clock = time.perf_counter()
-        net.zero_grad()
-        logits = net.forward_grid()
-        clock = lap("forward", clock)
+    def loss(self, lap=lambda name: None):
+        """the closure of train_xdg without the optimiser step: the loss tensor (the whole field's, the same on every rank; call
+        .backward() on it).  `lap(name)` is called as each part (TIMERS) ends."""
+        logits = self.net.forward_grid()
+        lap("forward")
         if self.hard:
             density = fem.satisfy_volume_constraint(logits, self._max_volume, mode=self.vcs, allsum=self._allsum, allmax=self._allmax)
         else:
             density = torch.clamp(logits, 0.0, 1.0)
-        clock = lap("satisfier", clock)
+        self.last_density = density.detach()
+        lap("satisfier")
         loss = _SlabCompliance.apply(density, self)
-        clock = lap("solve", clock)
+        lap("solve")
         if not self.hard:
             loss = loss + fem.satisfy_volume_constraint(density, self._max_volume, compliance_loss=loss.detach(), scaler_mode='clip',
                                                         constant=1500, mode=self.vcs, allsum=self._allsum)
-            clock = lap("satisfier", clock)
+            lap("satisfier")
+        return loss
+
+    def step(self, lr):
+        """one step of train_xdg's loop; returns the loss"""
+        t = dict.fromkeys(self.TIMERS, 0.0)
+        torch.cuda.synchronize()
+        clock = [time.perf_counter()]
+
+        def lap(name):
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            t[name] += now - clock[0]
+            clock[0] = now
+
+        self.net.zero_grad()
+        loss = self.loss(lap)
         loss.backward()
-        clock = lap("backward", clock)
-        net.adam_step(lr=float(lr))
-        lap("adam", clock)
+        lap("backward")
+        self.net.adam_step(lr=float(lr))
+        lap("adam")
         value = float(loss.detach())
-        self.steps.append(dict(t, loss=value, pcg_iterations=self._iterations))
+        self.steps.append(dict(t, loss=value, pcg_iterations=self.ds.last_iterations))
         return value
 
     def split(self):

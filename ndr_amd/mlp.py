@@ -279,16 +279,11 @@ class TrainableMLP(torch.nn.Module):
 
     @staticmethod
     def _all_reduce(grads):
-        import torch.distributed as dist
-        if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        from .slab_comm import SlabComm
+        comm = SlabComm()
+        if comm.world == 1:
             return grads
-        flat = torch.cat([g.reshape(-1) for g in grads])          # one all-reduce of the 1.57 M gradients
-        if dist.get_backend() == "gloo":
-            h = flat.cpu()
-            dist.all_reduce(h)
-            flat = h.to(flat.device)
-        else:
-            dist.all_reduce(flat)
+        flat = comm.all_reduce(torch.cat([g.reshape(-1) for g in grads]))          # one all-reduce of the 1.57 M gradients
         out, o = [], 0
         for g in grads:
             out.append(flat[o:o + g.numel()].reshape(g.shape))

@@ -279,7 +279,7 @@ def test_mlp_training_step_sharded_over_ranks_equals_whole_grid():
         assert err < 5e-3, (rank, err)       # fp16 operands: chunk boundaries differ between the two evaluations
 
 
-def _trainer_worker(rank, world, port, q):
+def _closure_worker(rank, world, port, sharded, q):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -287,7 +287,8 @@ def _trainer_worker(rank, world, port, q):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     torch.cuda.set_device(0)
     from helpers import BC_CANTILEVER, MATERIAL
-    from ndr_amd import distributed as vd, fem, pyVoxelFEM
+    from ndr_amd import fem, pyVoxelFEM
+    from ndr_amd.distributed_xdg import DistributedXdgLoop
     from ndr_amd.mlp import TrainableMLP
     grid, dom, v0, levels = (32, 16, 16), ([0.0, 0.0, 0.0], [2.0, 1.0, 1.0]), 0.5, 2
     torch.manual_seed(7)
@@ -295,13 +296,16 @@ def _trainer_worker(rank, world, port, q):
     with torch.no_grad():                                     # a non-trivial field: scale the output layer up
         net._linears()[-1].weight.mul_(3.0)
     # sharded evaluation of the closure
-    ds = vd.DistributedMGSolver(grid, dom[0], dom[1], BC_CANTILEVER, MATERIAL, levels)
-    tr = vd.DistributedDensityTrainer(ds, net, v0, tol=1e-9, zero_init=True)
+    loop = DistributedXdgLoop(MATERIAL, BC_CANTILEVER, [1, 1, 1], dom, grid, v0, levels)
+    assert loop.sharded                                       # T = 2: the hierarchy allows set_local_densities ...
+    loop.sharded = sharded                                    # ... and the gathered hand-off (set_global_densities) is run as well
+    loop.SOLVER = dict(loop.SOLVER, tol=1e-9, zeroInit=True)
+    loop.attach(net)
     net.zero_grad()
-    loss_d = tr.loss()
+    loss_d = loop.loss()
     loss_d.backward()
     gd = [p.grad.clone() for p in net.parameters()]
-    vol = float(tr._reduce(tr.last_density.sum().reshape(1), dist.ReduceOp.SUM)[0]) / (grid[0] * grid[1] * grid[2])
+    vol = float(loop.comm.all_reduce(loop.last_density.sum().reshape(1))[0]) / (grid[0] * grid[1] * grid[2])
     # the same closure in this process alone (fem.satisfy_volume_constraint + VoxelFEMFunction)
     tps = fem.initializeTensorProductSimulator([1, 1, 1], [np.array(dom[0]), np.array(dom[1])], list(grid), v0, 1, 1e-4, 3, MATERIAL, BC_CANTILEVER)
     obj = pyVoxelFEM.MultigridComplianceObjective(tps.multigridSolver(levels))
@@ -321,13 +325,15 @@ def _trainer_worker(rank, world, port, q):
     dist.destroy_process_group()
 
 
-def test_distributed_closure_equals_single_process_closure():
-    """train_xdg closure over 2 slab ranks: loss (2 J), volume and parameter gradients equal the single-process evaluation"""
+@pytest.mark.parametrize("sharded", [True, False])
+def test_distributed_closure_equals_single_process_closure(sharded):
+    """train_xdg closure over 2 slab ranks (DistributedXdgLoop.loss; densities to the solver sharded and gathered): loss (2 J),
+    volume and parameter gradients equal the single-process evaluation"""
     world = 2
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = __import__('helpers').free_port()
-    procs = [ctx.Process(target=_trainer_worker, args=(r, world, port, q)) for r in range(world)]
+    procs = [ctx.Process(target=_closure_worker, args=(r, world, port, sharded, q)) for r in range(world)]
     for p in procs:
         p.start()
     res = __import__('helpers').collect_from_ranks(q, procs)

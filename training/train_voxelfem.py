@@ -49,7 +49,10 @@ def main(argv=None):
         if args.optim != 'OC':
             ap.error('Optimizer {} is unknown or not implemented.'.format(args.optim))
         if 'WORLD_SIZE' not in os.environ:
-            return _launch_ranks(args.gpus, list(sys.argv[1:] if argv is None else argv), args, cfg, grid, v0)
+            from ndr_amd.distributed import launch_ranks
+            launch_ranks(args.gpus, main, list(sys.argv[1:] if argv is None else argv))
+            with open(os.path.join(args.out, 'loss', 'gt', str(args.jid), _title(args, cfg, grid, v0) + '.json')) as fh:
+                return json.load(fh)['compliance']              # what rank 0 wrote
         if int(os.environ['WORLD_SIZE']) != args.gpus:
             ap.error('--gpus {} does not match WORLD_SIZE {}'.format(args.gpus, os.environ['WORLD_SIZE']))
     from ndr_amd import fem
@@ -84,7 +87,7 @@ def _title(args, cfg, grid, v0):
 
 
 def _run_ranks(args, cfg, grid, v0, levels):
-    """this process is one rank (environment of torch.distributed.run or of _launch_ranks): the loop of fem.ground_truth_topopt
+    """this process is one rank (environment of torch.distributed.run or of distributed.launch_ranks): the loop of fem.ground_truth_topopt
     on the slabs; returns (gathered densities on rank 0, final compliance, thresholded compliance, history, rank)"""
     import torch
     import torch.distributed as dist
@@ -106,33 +109,6 @@ def _run_ranks(args, cfg, grid, v0, levels):
     return densities, final, binary, loop.history, rank
 
 
-def _rank_main(rank, world, port, argv):
-    """entry of a rank process started by `_launch_ranks` (fresh interpreter, nothing has touched the GPU yet)"""
-    os.environ.update({'RANK': str(rank), 'LOCAL_RANK': str(rank), 'WORLD_SIZE': str(world), 'MASTER_ADDR': '127.0.0.1',
-                       'MASTER_PORT': str(port), 'HSA_ENABLE_IPC_MODE_LEGACY': os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY', '0')})
-    main(argv)
-
-
-def _launch_ranks(world, argv, args, cfg, grid, v0):
-    """--gpus N without a launcher: start N rank processes (spawn: fresh children; this parent never initialises the GPU), wait
-    for them and return the compliance history rank 0 wrote"""
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as sk:
-        sk.bind(('127.0.0.1', 0))
-        port = sk.getsockname()[1]
-    ctx = mp.get_context('spawn')
-    procs = [ctx.Process(target=_rank_main, args=(r, world, port, argv)) for r in range(world)]
-    for pr in procs:
-        pr.start()
-    code = 0
-    for pr in procs:
-        pr.join()
-        code = max(code, abs(pr.exitcode or 0))
-    if code:
-        raise SystemExit('a rank process failed (exit code {})'.format(code))
-    with open(os.path.join(args.out, 'loss', 'gt', str(args.jid), _title(args, cfg, grid, v0) + '.json')) as fh:
-        return json.load(fh)['compliance']
 
 if __name__ == '__main__':
     main()

@@ -54,7 +54,10 @@ def main(argv=None):
     if args.gpus > 1:
         _refuse_undecomposable(ap, args, cfg, grid)
         if 'WORLD_SIZE' not in os.environ:
-            return _launch_ranks(args.gpus, list(sys.argv[1:] if argv is None else argv), args)
+            from ndr_amd.distributed import launch_ranks
+            launch_ranks(args.gpus, main, list(sys.argv[1:] if argv is None else argv))
+            with open(os.path.join(args.out, 'weights', 'ff', str(args.jid), '{}_loss.json'.format(args.jid))) as fh:
+                return json.load(fh)              # what rank 0 wrote
         if int(os.environ['WORLD_SIZE']) != args.gpus:
             ap.error('--gpus {} does not match WORLD_SIZE {}'.format(args.gpus, os.environ['WORLD_SIZE']))
         return _train_ranks(args, cfg, grid, v0)
@@ -155,7 +158,7 @@ def _refuse_undecomposable(ap, args, cfg, grid):
 
 
 def _train_ranks(args, cfg, grid, v0):
-    """this process is one rank (environment of torch.distributed.run or of _launch_ranks): the loop of main on the slabs;
+    """this process is one rank (environment of torch.distributed.run or of distributed.launch_ranks): the loop of main on the slabs;
     rank 0 prints and writes what the one-GPU run writes"""
     import torch.distributed as dist
     from ndr_amd import distributed, fem
@@ -200,35 +203,6 @@ def _train_ranks(args, cfg, grid, v0):
     finally:
         dist.destroy_process_group()
     return history
-
-
-def _rank_main(rank, world, port, argv):
-    """entry of a rank process started by `_launch_ranks` (fresh interpreter, nothing has touched the GPU yet)"""
-    os.environ.update({'RANK': str(rank), 'LOCAL_RANK': str(rank), 'WORLD_SIZE': str(world), 'MASTER_ADDR': '127.0.0.1',
-                       'MASTER_PORT': str(port), 'HSA_ENABLE_IPC_MODE_LEGACY': os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY', '0')})
-    main(argv)
-
-
-def _launch_ranks(world, argv, args):
-    """--gpus N without a launcher: start N rank processes (spawn: fresh children; this parent never initialises the GPU), wait
-    for them and return the loss history rank 0 wrote"""
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as sk:
-        sk.bind(('127.0.0.1', 0))
-        port = sk.getsockname()[1]
-    ctx = mp.get_context('spawn')
-    procs = [ctx.Process(target=_rank_main, args=(r, world, port, argv)) for r in range(world)]
-    for pr in procs:
-        pr.start()
-    code = 0
-    for pr in procs:
-        pr.join()
-        code = max(code, abs(pr.exitcode or 0))
-    if code:
-        raise SystemExit('a rank process failed (exit code {})'.format(code))
-    with open(os.path.join(args.out, 'weights', 'ff', str(args.jid), '{}_loss.json'.format(args.jid))) as fh:
-        return json.load(fh)
 
 
 if __name__ == '__main__':
