@@ -127,7 +127,7 @@ class HipLocalOps:
         from . import pyVoxelFEM as pv
         lo, hi = part.local_bbox(bbmin, bbmax)
         self.tps = pv.TensorProductSimulator1_1_1([lo, hi], list(part.local_ne))
-        _lib.check(self.tps._lib.vfem_sim_set_isotropic(self.tps._h, young, poisson))
+        _lib.check(self.tps._c("set_isotropic")(self.tps._h, young, poisson))
         self.tps.E_0, self.tps.E_min, self.tps.gamma = E0, Emin, gamma
         self.device = torch.device("cuda", torch.cuda.current_device())
 
@@ -139,7 +139,7 @@ class HipLocalOps:
 
     def apply_planes(self, u, out, lo, hi):
         """output node planes lo..hi (inclusive) only"""
-        _lib.check(self.tps._lib.vfem_sim_apply_k_planes(self.tps._h, _ptr(u), _ptr(out), int(lo), int(hi), _stream()))
+        _lib.check(self.tps._c("apply_k_planes")(self.tps._h, _ptr(u), _ptr(out), int(lo), int(hi), _stream()))
 
 
 class DistributedStiffness:
@@ -476,8 +476,8 @@ class DistributedMGSolver:
         self.gmg = ctypes.c_void_p()
         _lib.check(self.lib.vfem_mg_create_partial(ctypes.byref(self.gmg), self.gsim._h, self.L, self.T))
         g0 = self.geom[0]
-        _lib.check(self.lib.vfem_sim_set_next_element_padding(g0.extra_lo, g0.extra_hi))
-        self.lsim = material(pv.TensorProductSimulator1_1_1(local_box, [g0.nx, self.ne[1], self.ne[2]]))
+        self.lsim = material(pv.TensorProductSimulator1_1_1(local_box, [g0.nx, self.ne[1], self.ne[2]],
+                                                            _element_padding=(g0.extra_lo, g0.extra_hi)))
         # per-level local Dirichlet masks = slices of the global coarsened masks
         masks = []
         for l, g in enumerate(self.geom):

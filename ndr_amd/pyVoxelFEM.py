@@ -6,6 +6,11 @@ float64 numpy arrays (copied, like the Eigen conversions of the reference), the 
 ``libvfem.so`` (HIP kernels, include/vfem.h) on device memory held in torch tensors.
 ``*_device`` methods take/return torch CUDA tensors without copies.
 
+One simulator class (``_Simulator``) and one multigrid class (``_MultigridSolver``) bind every element type: they are
+parameterised by ``N``, ``P`` and the prefix of the C entry points, resolved by ``_c(name)`` / ``_mg(name)``.  The tuned
+<1,1,1> path (``vfem_sim_`` / ``vfem_mg_``) and the generic path (``vfem_gsim_`` / ``vfem_gmg_``: 2-D and degree 2) are
+subclasses that hold only what differs between the two C layers.
+
 Host-side pieces (BC/material parsing, filters, volume constraint, optimality-criterion update,
 problem cache) restate ``TopologyOptimization{Problem,Filter,Constraint}.hh`` and
 ``OptimalityCriterion.hh``; SURVEY 8(f)-1 ranks moving them to the device as the next step.
@@ -212,45 +217,302 @@ def _factorize(mode, band_bytes):
 
 
 # ----------------------------------------------------------------------------------------------
-# TensorProductSimulator<1,1,1>
+# MultigridSolver<p,..,p>
 # ----------------------------------------------------------------------------------------------
 
-class TensorProductSimulator1_1_1:
-    """``pyVoxelFEM.detail.TensorProductSimulator1_1_1`` (VoxelFEM.cc:48-92; TPS.hh:219-1419)."""
+class _LevelView:
+    """What ``MultigridSolver.getSimulator(l)`` exposes for coarse levels (sizes + Dirichlet mask)."""
 
-    N = 3
+    def __init__(self, mg, l):
+        self._mg, self._l = mg, l
 
-    def __init__(self, domainBoundingBox, numElemg):
-        _lib.require_gpu()
+    def numNodes(self):
+        return self._mg._nn(self._l)
+
+    def NbElementsPerDimension(self):
+        ne = (ctypes.c_int64 * 3)()
+        _lib.check(self._mg._mg("level_dims")(self._mg._h, self._l, ne))
+        return np.array(list(ne)[:self._mg.N], dtype=np.int64)
+
+    def numElements(self):
+        return int(np.prod(self.NbElementsPerDimension()))
+
+    @property
+    def dirichletMask(self):
+        m = np.empty(self.numNodes(), dtype=np.uint8)
+        _lib.check(self._mg._mg("level_dirichlet_mask")(self._mg._h, self._l, m.ctypes.data_as(ctypes.c_void_p)))
+        return np.stack([(m >> c) & 1 for c in range(self._mg.N)], axis=1).astype(bool)
+
+
+class _MultigridSolver:
+    """MultigridSolver<p,..,p> (VoxelFEM.cc:94-131; MG.hh:11-759) over the hierarchy handles of ``libvfem``.  The two
+    subclasses name the C entry points (``_MG_PREFIX``) and hold what only one of the paths has."""
+
+    _MG_PREFIX = None              # "vfem_mg_" (tuned <1,1,1>) or "vfem_gmg_" (generic path)
+
+    def __init__(self, tps, numCoarseningLevels):
         self._lib = _lib.load()
-        lo = np.asarray(domainBoundingBox[0], dtype=np.float64).reshape(-1)
-        hi = np.asarray(domainBoundingBox[1], dtype=np.float64).reshape(-1)
-        ne = [int(v) for v in numElemg]
-        if len(ne) != 3 or lo.size != 3 or hi.size != 3:
-            raise RuntimeError("Dimension mismatch: %d vs 3" % len(ne))
-        self._bbmin, self._bbmax = lo.copy(), hi.copy()
-        self._ne = np.array(ne, dtype=np.int64)
-        self._nn = self._ne + 1
+        self._tps = tps                      # keeps the fine simulator alive (MG.hh:32,88)
+        self.N = tps.N
         h = ctypes.c_void_p()
-        _lib.check(self._lib.vfem_sim_create(
-            ctypes.byref(h), lo.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-            hi.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-            self._ne.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        _lib.check(self._mg("create")(ctypes.byref(h), tps._h, int(numCoarseningLevels)))
         self._h = h
-        self._E0, self._Emin, self._gamma = 1.0, 1e-9, 3.0           # TPS.hh:1392-1394
-        self._mask = np.zeros((self.numNodes(), 3), dtype=bool)
-        self._dvals = np.zeros((self.numNodes(), 3))
-        self._loads = torch.zeros((self.numNodes(), 3), dtype=torch.float64, device=_dev())
-        self._has_force = None
+        self.L = int(numCoarseningLevels)
+        self.buildBlockStiffnessMatrices = True
+        self.buildFinestBlockStiffnessMatrix = False
+        self.last_iterations = 0
+        self.last_relative_residual = 0.0
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value:
             try:
-                self._lib.vfem_sim_destroy(h)
+                self._mg("destroy")(h)
             except Exception:
                 pass
             self._h = None
+
+    def _mg(self, name):
+        return getattr(self._lib, self._MG_PREFIX + name)
+
+    def _nn(self, l):
+        n = int(self._mg("level_num_nodes")(self._h, int(l)))
+        if n < 0:
+            raise IndexError("vector::_M_range_check")      # m_sims.at(l)
+        return n
+
+    def getSimulator(self, l):
+        self._nn(l)
+        return self._tps if int(l) == 0 else _LevelView(self, int(l))
+
+    def setSymmetricGaussSeidel(self, symmetric):
+        self._mg("set_symmetric_gauss_seidel")(self._h, int(bool(symmetric)))
+
+    def updateElementStiffnessMatrices(self):
+        _lib.check(self._mg("update_operators")(self._h, _stream()))
+
+    updateBlockKs = updateElementStiffnessMatrices
+
+    # ---- per-operator entry points (device variants first) ----
+    def applyK_device(self, l, u):
+        u = _to_dev(u, (self._nn(l), self.N))
+        out = torch.empty_like(u)
+        _lib.check(self._mg("apply_k")(self._h, int(l), _ptr(u), _ptr(out), _stream()))
+        return out
+
+    def applyK(self, l, u):
+        return _to_np(self.applyK_device(l, u))
+
+    def computeResidual_device(self, l, u, b):
+        u = _to_dev(u, (self._nn(l), self.N))
+        b = _to_dev(b, (self._nn(l), self.N))
+        r = torch.empty_like(u)
+        _lib.check(self._mg("residual")(self._h, int(l), _ptr(u), _ptr(b), _ptr(r), _stream()))
+        return r
+
+    def computeResidual(self, l, u, b):
+        return _to_np(self.computeResidual_device(l, u, b))
+
+    def smoothing_device(self, l, u, b, forward=True):
+        u = _to_dev(u, (self._nn(l), self.N)).clone()
+        b = _to_dev(b, (self._nn(l), self.N))
+        _lib.check(self._mg("smooth")(self._h, int(l), _ptr(u), _ptr(b), int(bool(forward)), _stream()))
+        return u
+
+    def smoothing(self, l, u, b):
+        """Bound as updateElementStiffnessMatrices + one forward sweep on a copy (VoxelFEM.cc:99-104).  The
+        reference binding runs the sequential sweep (MG.hh:269-282); the solver itself uses the multicoloured
+        sweep (MG.hh:336-340), which is what this returns."""
+        self.updateElementStiffnessMatrices()
+        return _to_np(self.smoothing_device(l, u, b, True))
+
+    def zeroOutDirichletComponents(self, l, u):
+        t = _to_dev(u, (self._nn(l), self.N)).clone()
+        _lib.check(self._mg("zero_dirichlet")(self._h, int(l), _ptr(t), _stream()))
+        return _to_np(t)
+
+    def restriction_device(self, fine_level, values):
+        v = _to_dev(values, (self._nn(fine_level), self.N))
+        out = torch.empty((self._nn(fine_level + 1), self.N), dtype=torch.float64, device=_dev())
+        _lib.check(self._mg("restrict")(self._h, int(fine_level), _ptr(v), _ptr(out), _stream()))
+        return out
+
+    def interpolation_device(self, fine_level, values, out=None):
+        v = _to_dev(values, (self._nn(fine_level + 1), self.N))
+        acc = out is not None
+        if out is None:
+            out = torch.empty((self._nn(fine_level), self.N), dtype=torch.float64, device=_dev())
+        _lib.check(self._mg("interpolate")(self._h, int(fine_level), _ptr(v), _ptr(out), int(acc), _stream()))
+        return out
+
+    def debugMulticolorVisit(self):
+        """Visit order of the multicoloured sweep on level 0 (MG.hh:285-334): one colour per local node index of the
+        element; along an axis the nodes of an element boundary (local index 0 or p) recur every 2p nodes, interior ones
+        every p."""
+        nn, p, N = tuple(self._tps._nn), self._tps.P, self.N
+        result = np.zeros(nn, dtype=np.int32)
+        counter = 0
+        for lni in np.ndindex(*([p + 1] * N)):
+            sl = tuple(slice(lni[d], None, (2 if lni[d] in (0, p) else 1) * p) for d in range(N))
+            sub = result[sl]
+            sub[...] = counter + np.arange(sub.size).reshape(sub.shape)
+            counter += sub.size
+        return result.reshape(-1)
+
+    # ---- solvers ----
+    def solve_device(self, u, f, numSteps, numSmoothingSteps, stiffnessUpdated=False, zeroDirichlet=False,
+                     it_callback=None, fullMultigrid=False):
+        x = _to_dev(u, (self._nn(0), self.N)).clone()
+        f = _to_dev(f, (self._nn(0), self.N))
+        if it_callback is None:
+            _lib.check(self._mg("solve")(self._h, _ptr(x), _ptr(f), int(numSteps), int(numSmoothingSteps),
+                                         int(bool(stiffnessUpdated)), int(bool(zeroDirichlet)),
+                                         int(bool(fullMultigrid)), _stream()))
+            return x
+        for i in range(int(numSteps)):
+            _lib.check(self._mg("solve")(self._h, _ptr(x), _ptr(f), 1, int(numSmoothingSteps),
+                                         int(bool(stiffnessUpdated) or i > 0), int(bool(zeroDirichlet)),
+                                         int(bool(fullMultigrid) and i == 0), _stream()))
+            it_callback(i, _to_np(x))
+        return x
+
+    def solve(self, u, f, numSteps, numSmoothingSteps, stiffnessUpdated=False, zeroDirichlet=False,
+              it_callback=None, fullMultigrid=False):
+        return _to_np(self.solve_device(u, f, numSteps, numSmoothingSteps, stiffnessUpdated, zeroDirichlet,
+                                        it_callback, fullMultigrid))
+
+    def _pcg_check_inputs(self, u, b):
+        """what a path rejects before x and b are converted (nothing here)"""
+
+    def _pcg_search_direction(self):
+        """third argument of the PCG ``it_callback``: the generic path does not expose its search direction"""
+        return None
+
+    def preconditionedConjugateGradient_device(self, u, b, maxIter, tol, it_callback=None, mgIterations=1,
+                                               mgSmoothingIterations=1, fullMultigrid=False, residual_cb=None):
+        self._pcg_check_inputs(u, b)
+        x = _to_dev(u).reshape(-1, self.N).clone()
+        b = _to_dev(b).reshape(-1, self.N)
+        if x.shape[0] != b.shape[0]:
+            raise RuntimeError("x and b should have the same size")
+        if x.shape[0] != self._nn(0):
+            raise RuntimeError("size of input and number of nodes don't correspond")
+        its = ctypes.c_int(0)
+        rel = ctypes.c_double(0.0)
+
+        def _cb(_user, it, rnorm):
+            if residual_cb is not None:
+                residual_cb(it, rnorm)
+            if it_callback is not None:
+                it_callback(it, _to_np(x), self._pcg_search_direction())
+
+        cb = _lib.RESIDUAL_CB(_cb) if (residual_cb is not None or it_callback is not None) else _lib.RESIDUAL_CB()
+        _lib.check(self._mg("pcg")(self._h, _ptr(x), _ptr(b), int(maxIter), float(tol), int(mgIterations),
+                                   int(mgSmoothingIterations), int(bool(fullMultigrid)), cb, None,
+                                   ctypes.byref(its), ctypes.byref(rel), _stream()))
+        self.last_iterations = its.value
+        self.last_relative_residual = rel.value
+        return x
+
+    def preconditionedConjugateGradient(self, u, b, maxIter, tol, it_callback=None, mgIterations=1,
+                                        mgSmoothingIterations=1, fullMultigrid=False):
+        return _to_np(self.preconditionedConjugateGradient_device(u, b, maxIter, tol, it_callback, mgIterations,
+                                                                  mgSmoothingIterations, fullMultigrid))
+
+
+class MultigridSolver1_1_1(_MultigridSolver):
+    """``pyVoxelFEM.detail.MultigridSolver1_1_1``: the tuned hierarchy (``vfem_mg_*``), which also exposes its coarsest
+    solve and its work vectors."""
+
+    _MG_PREFIX = "vfem_mg_"
+
+    def coarsestSolve_device(self, b):
+        b = _to_dev(b, (self._nn(self.L), 3))
+        x = torch.empty_like(b)
+        _lib.check(self._mg("coarsest_solve")(self._h, _ptr(b), _ptr(x), _stream()))
+        return x
+
+    def _field(self, which, l):
+        n = self._nn(l) if which != 2 else self._nn(0)
+        p = self._mg("field_ptr")(self._h, which, int(l))
+        out = torch.empty((n, 3), dtype=torch.float64, device=_dev())
+        _lib.check(self._lib.vfem_copy_d2d(_ptr(out), ctypes.c_void_p(p), n * 3 * 8, _stream()))
+        return out
+
+    def debug_get_x(self, l):
+        return _to_np(self._field(0, l))
+
+    def debug_get_b(self, l):
+        return _to_np(self._field(1, l))
+
+    def _pcg_check_inputs(self, u, b):
+        if isinstance(u, torch.Tensor) and isinstance(b, torch.Tensor) and u.shape != b.shape:
+            raise RuntimeError("x and b should have the same size")
+
+    def _pcg_search_direction(self):
+        return _to_np(self._field(2, 0))
+
+
+class _GenericMultigridSolver(_MultigridSolver):
+    """MultigridSolver<p,..,p> on the generic path (``vfem_gmg_*``)."""
+
+    _MG_PREFIX = "vfem_gmg_"
+
+
+# ----------------------------------------------------------------------------------------------
+# TensorProductSimulator<p,..,p>
+# ----------------------------------------------------------------------------------------------
+
+class _Simulator:
+    """TensorProductSimulator<p,..,p> (VoxelFEM.cc:48-92; TPS.hh:219-1419) over a simulator handle of ``libvfem``: N
+    dimensions, degree P.  The two subclasses name the C entry points (``_SIM_PREFIX``), create the handle and hold what
+    only one of the paths has."""
+
+    N = 3
+    P = 1
+    _SIM_PREFIX = None             # "vfem_sim_" (tuned <1,1,1>) or "vfem_gsim_" (generic path)
+    _COMPLIANCE = None             # full name of the compliance entry point (the tuned one has no "sim_" in its name)
+    _MG_CLASS = None
+    # whether <prefix>get_densities writes every STORED element (node-grid elements + slab padding) or numElements() only:
+    # getDensities_device sizes its result by it, a buffer sized the other way round would be overrun
+    _GET_DENSITIES_WRITES_STORED = None
+
+    def __init__(self, domainBoundingBox, numElemg, _element_padding=(0, 0)):
+        """``_element_padding`` (slab decomposition, ndr_amd/distributed*.py): element layers kept below / above the node
+        grid along x in the density array only (``setElementDensities_padded``)"""
+        _lib.require_gpu()
+        self._lib = _lib.load()
+        N = self.N
+        lo = np.asarray(domainBoundingBox[0], dtype=np.float64).reshape(-1)
+        hi = np.asarray(domainBoundingBox[1], dtype=np.float64).reshape(-1)
+        ne = [int(v) for v in numElemg]
+        if len(ne) != N or lo.size != N or hi.size != N:
+            raise RuntimeError("Dimension mismatch: %d vs %d" % (len(ne), N))
+        self._bbmin, self._bbmax = lo.copy(), hi.copy()
+        self._ne = np.array(ne, dtype=np.int64)
+        self._nn = self.P * self._ne + 1
+        h = ctypes.c_void_p()
+        _lib.check(self._create(ctypes.byref(h), lo.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                hi.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                self._ne.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                int(_element_padding[0]), int(_element_padding[1])))
+        self._h = h
+        self._E0, self._Emin, self._gamma = 1.0, 1e-9, 3.0           # TPS.hh:1392-1394
+        self._mask = np.zeros((self.numNodes(), N), dtype=bool)
+        self._dvals = np.zeros((self.numNodes(), N))
+        self._loads = torch.zeros((self.numNodes(), N), dtype=torch.float64, device=_dev())
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                self._c("destroy")(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def _c(self, name):
+        return getattr(self._lib, self._SIM_PREFIX + name)
 
     # ---- sizes / geometry ----
     def numNodes(self):
@@ -272,73 +534,78 @@ class TensorProductSimulator1_1_1:
     def elementNodes(self, ei):
         e = np.array(np.unravel_index(int(ei), tuple(self._ne)))
         out = []
-        for m in range(8):
-            loc = np.array([(m >> 2) & 1, (m >> 1) & 1, m & 1])
-            out.append(int(np.ravel_multi_index(tuple(e + loc), tuple(self._nn))))
+        for loc in np.ndindex(*([self.P + 1] * self.N)):
+            out.append(int(np.ravel_multi_index(tuple(self.P * e + np.array(loc)), tuple(self._nn))))
         return np.array(out, dtype=np.uint64)
 
     def elemNodeGlobalIndex(self, ei, n):
         return int(self.elementNodes(ei)[int(n)])
 
+    def _first_nodes(self):
+        """(flat index of the first node of every element, node strides)"""
+        eidx = np.stack(np.meshgrid(*[np.arange(n) for n in self._ne], indexing="ij"), -1).reshape(-1, self.N)
+        nstr = np.array([int(np.prod(self._nn[d + 1:])) for d in range(self.N)])
+        return (self.P * eidx) @ nstr, nstr
+
     def getMesh(self):
-        """(V, F): node positions and 8-node hexahedra in Gmsh ordering (TPS.hh:531-565)."""
-        idx = np.stack(np.meshgrid(*[np.arange(n) for n in self._nn], indexing="ij"), -1).reshape(-1, 3)
+        """(V, F): all node positions; per element its corner nodes in Gmsh quad / hexahedron order (TPS.hh:531-565)"""
+        N, p = self.N, self.P
+        idx = np.stack(np.meshgrid(*[np.arange(n) for n in self._nn], indexing="ij"), -1).reshape(-1, N)
         V = self._bbmin + idx * (self._bbmax - self._bbmin) / (self._nn - 1.0)
-        eidx = np.stack(np.meshgrid(*[np.arange(n) for n in self._ne], indexing="ij"), -1).reshape(-1, 3)
-        nstr = np.array([self._nn[1] * self._nn[2], self._nn[2], 1])
-        first = eidx @ nstr
-        loc = [np.array([(m >> 2) & 1, (m >> 1) & 1, m & 1]) @ nstr for m in range(8)]
-        order = [0, 1, 3, 2, 4, 5, 7, 6]
-        F = np.stack([first + loc[m] for m in order], axis=1)
+        first, nstr = self._first_nodes()
+        corners = [(0, 0), (1, 0), (1, 1), (0, 1)] if N == 2 else \
+            [(0, 0, 0), (0, 0, 1), (0, 1, 1), (0, 1, 0), (1, 0, 0), (1, 0, 1), (1, 1, 1), (1, 1, 0)]
+        F = np.stack([first + (p * np.array(c)) @ nstr for c in corners], axis=1)
         return V, F
 
     # ---- material / SIMP ----
     def readMaterial(self, materialPath):
         young, poisson = _read_isotropic_material(materialPath)
         self._young, self._poisson = young, poisson
-        _lib.check(self._lib.vfem_sim_set_isotropic(self._h, young, poisson))
+        _lib.check(self._c("set_isotropic")(self._h, young, poisson))
         self._direct_mg = None                    # the reference resets its solver when the operator changes (TPS.hh:404)
 
     def _push_simp(self):
-        _lib.check(self._lib.vfem_sim_set_simp(self._h, self._E0, self._Emin, self._gamma))
+        _lib.check(self._c("set_simp")(self._h, self._E0, self._Emin, self._gamma))
 
     def _lame(self):
+        """ElasticityTensor::setIsotropic (ElasticityTensor.hh:100-133): 3-D Lame parameters, plane stress in 2-D"""
         E, nu = getattr(self, "_young", 1.0), getattr(self, "_poisson", 0.0)         # ETensor(1, 0) default, TPS.hh:1379
-        return nu * E / ((1.0 + nu) * (1.0 - 2.0 * nu)), E / (2.0 + 2.0 * nu)
+        lam = nu * E / ((1.0 + nu) * (1.0 - 2.0 * nu)) if self.N == 3 else nu * E / (1.0 - nu * nu)
+        return lam, E / (2.0 + 2.0 * nu)
 
     def readDensities(self, materialPath, fieldName="density"):
         """TPS::readDensities (VoxelFEM.cc:54)"""
-        self.setElementDensities(_densities_from_msh(materialPath, fieldName, self._ne, 3))
+        self.setElementDensities(_densities_from_msh(materialPath, fieldName, self._ne, self.N))
 
     def constantStrainLoad(self, eps):
         """TPS::constantStrainLoad (VoxelFEM.cc:66), evaluated on the device"""
         lam, mu = self._lame()
         rho = self.getDensities_device()[:self.numElements()].reshape(tuple(int(n) for n in self._ne))
-        return _to_np(_constant_strain_load(eps, lam, mu, (self._bbmax - self._bbmin) / self._ne, 1, rho))
+        return _to_np(_constant_strain_load(eps, lam, mu, (self._bbmax - self._bbmin) / self._ne, self.P, rho))
+
+    @property
+    def _GETK_MAX_ELEMENTS(self):
+        """largest grid getK assembles: 2^30 entries of element matrices (the tuned class keeps its own, lower cap)"""
+        return (1 << 30) // (self.P + 1) ** (2 * self.N)
 
     def getK(self):
         """TPS::getK (VoxelFEM.cc:62): assembled stiffness matrix, upper triangle, compressed columns (host, small grids)"""
-        if self.numElements() > (1 << 21):
+        if self.numElements() > self._GETK_MAX_ELEMENTS:
             raise RuntimeError("getK assembles on the host; use applyK for grids of this size")
         rho = self.getDensities()[:self.numElements()]
         young = self._Emin + rho ** self._gamma * (self._E0 - self._Emin)
-        nodes = np.stack([self.elementNodes(0) - 0], 0).astype(np.int64)
-        eidx = np.stack(np.meshgrid(*[np.arange(n) for n in self._ne], indexing="ij"), -1).reshape(-1, 3)
-        nstr = np.array([self._nn[1] * self._nn[2], self._nn[2], 1])
-        nodes = (eidx @ nstr)[:, None] + nodes
-        return _assemble_upper(nodes, self.fullDensityElementStiffnessMatrix(), young, 3, self.numNodes())
+        nodes = self._first_nodes()[0][:, None] + self.elementNodes(0).astype(np.int64)[None, :]
+        return _assemble_upper(nodes, self.fullDensityElementStiffnessMatrix(), young, self.N, self.numNodes())
 
     E_0 = property(lambda s: s._E0, lambda s, v: (setattr(s, "_E0", float(v)), s._push_simp())[0])
     E_min = property(lambda s: s._Emin, lambda s, v: (setattr(s, "_Emin", float(v)), s._push_simp())[0])
     gamma = property(lambda s: s._gamma, lambda s, v: (setattr(s, "_gamma", float(v)), s._push_simp())[0])
 
-    @property
-    def ETensor(self):
-        raise RuntimeError("ETensor objects are not exposed; use readMaterial (isotropic materials)")
-
     def fullDensityElementStiffnessMatrix(self):
-        K0 = np.empty((24, 24))
-        _lib.check(self._lib.vfem_sim_k0(self._h, K0.ctypes.data_as(ctypes.c_void_p)))
+        ke = self.N * (self.P + 1) ** self.N
+        K0 = np.empty((ke, ke))
+        _lib.check(self._c("k0")(self._h, K0.ctypes.data_as(ctypes.c_void_p)))
         return K0
 
     def elementStiffnessMatrix(self, ei):
@@ -349,24 +616,30 @@ class TensorProductSimulator1_1_1:
         pass
 
     # ---- densities ----
+    def _num_stored_elements(self):
+        """elements of the density array: those of the node grid plus the padding layers of a slab simulator"""
+        return int(self._c("num_stored_elements")(self._h))
+
     def setUniformDensities(self, density):
-        _lib.check(self._lib.vfem_sim_set_uniform_density(self._h, float(density), _stream()))
+        if density > 1.0 or density < 0:
+            raise RuntimeError("Density value (%f) has to be in between 0 and 1" % density)
+        self.setElementDensities_padded(torch.full((self._num_stored_elements(),), float(density), dtype=torch.float64,
+                                                   device=_dev()))
 
     def setElementDensities(self, rho):
-        if int(self._lib.vfem_sim_num_stored_elements(self._h)) != self.numElements():
-            raise RuntimeError("padded slab simulator: use setElementDensities_padded")
-        t = _to_dev(rho, (self.numElements(),))
-        _lib.check(self._lib.vfem_sim_set_densities(self._h, _ptr(t), _stream()))
+        if self._num_stored_elements() != self.numElements():
+            raise RuntimeError("this simulator stores padding element layers: use setElementDensities_padded")
+        self.setElementDensities_padded(rho)
 
     def setElementDensities_padded(self, rho):
-        """slab simulators: densities for every stored element layer (node grid + padding)"""
-        n = int(self._lib.vfem_sim_num_stored_elements(self._h))
-        t = _to_dev(rho, (n,))
-        _lib.check(self._lib.vfem_sim_set_densities(self._h, _ptr(t), _stream()))
+        """all stored element layers (padding below, the node grid's elements, padding above), x slowest"""
+        t = _to_dev(rho, (self._num_stored_elements(),))
+        _lib.check(self._c("set_densities")(self._h, _ptr(t), _stream()))
 
     def getDensities_device(self):
-        t = torch.empty(int(self._lib.vfem_sim_num_stored_elements(self._h)), dtype=torch.float64, device=_dev())
-        _lib.check(self._lib.vfem_sim_get_densities(self._h, _ptr(t), _stream()))
+        n = self._num_stored_elements() if self._GET_DENSITIES_WRITES_STORED else self.numElements()
+        t = torch.empty(n, dtype=torch.float64, device=_dev())
+        _lib.check(self._c("get_densities")(self._h, _ptr(t), _stream()))
         return t
 
     def getDensities(self):
@@ -375,53 +648,54 @@ class TensorProductSimulator1_1_1:
     def setElementDensity(self, ei, value):
         t = self.getDensities_device()
         t[int(ei)] = float(value)
-        _lib.check(self._lib.vfem_sim_set_densities(self._h, _ptr(t), _stream()))
+        # what came back is either the stored array or the unpadded one (which a padded simulator refuses)
+        (self.setElementDensities_padded if self._GET_DENSITIES_WRITES_STORED else self.setElementDensities)(t)
 
     def elementDensity(self, ei):
         return float(self.getDensities_device()[int(ei)].item())
 
     # ---- boundary conditions ----
     def _push_dirichlet(self):
-        m = (self._mask[:, 0].astype(np.uint8) | (self._mask[:, 1].astype(np.uint8) << 1) |
-             (self._mask[:, 2].astype(np.uint8) << 2))
-        m = np.ascontiguousarray(m)
+        m = np.zeros(self.numNodes(), dtype=np.uint8)
+        for c in range(self.N):
+            m |= self._mask[:, c].astype(np.uint8) << c
         vals = np.ascontiguousarray(self._dvals)
-        _lib.check(self._lib.vfem_sim_set_dirichlet(self._h, m.ctypes.data_as(ctypes.c_void_p),
-                                                   vals.ctypes.data_as(ctypes.c_void_p)))
+        _lib.check(self._c("set_dirichlet")(self._h, m.ctypes.data_as(ctypes.c_void_p),
+                                            vals.ctypes.data_as(ctypes.c_void_p)))
         self._direct_mg = None                    # coarse Dirichlet masks of a cached hierarchy would be stale (TPS.hh:404)
 
     def _push_loads(self):
-        _lib.check(self._lib.vfem_sim_set_loads(self._h, _ptr(self._loads), _stream()))
+        """mirror ``_loads`` into the C simulator where it keeps a copy (the tuned path)"""
 
     def applyDisplacementsAndLoadsFromFile(self, bcPath):
         """applyDisplacementsAndLoads (TPS.hh:358-409): inclusive box test on node coordinates; forces are
-        split evenly over the matched nodes; Dirichlet components merge, conflicting values throw."""
+        split evenly over the matched nodes; Dirichlet components merge, conflicting values throw.  Force regions are
+        written on the device: a host copy of the loads of a 513^3 grid would be 3.2 GB."""
+        N = self.N
         size = self._bbmax - self._bbmin
         spacing = size / (self._nn - 1.0)
-        coords = [self._bbmin[d] + np.arange(self._nn[d]) * spacing[d] for d in range(3)]
+        coords = [self._bbmin[d] + np.arange(self._nn[d]) * spacing[d] for d in range(N)]
         shape = tuple(self._nn)
-        mask3 = self._mask.reshape(shape + (3,))
-        vals3 = self._dvals.reshape(shape + (3,))
-        loads = self._loads.reshape(shape + (3,))
+        mask3 = self._mask.reshape(shape + (N,))
+        vals3 = self._dvals.reshape(shape + (N,))
+        loads = self._loads.reshape(shape + (N,))
         for kind, comps, value, lo, hi, relative in _parse_regions(bcPath):
-            lo, hi = np.array(lo[:3]), np.array(hi[:3])
+            lo, hi = np.array(lo[:N]), np.array(hi[:N])
             if relative:
                 lo, hi = self._bbmin + lo * size, self._bbmin + hi * size
-            sel = [np.flatnonzero((coords[d] >= lo[d]) & (coords[d] <= hi[d])) for d in range(3)]
+            sel = [np.flatnonzero((coords[d] >= lo[d]) & (coords[d] <= hi[d])) for d in range(N)]
             count = int(np.prod([s.size for s in sel]))
             if kind == "force":
                 if count == 0:
                     raise RuntimeError("Force constraint region unmatched")
-                ix = torch.from_numpy(sel[0]).to(_dev())
-                iy = torch.from_numpy(sel[1]).to(_dev())
-                iz = torch.from_numpy(sel[2]).to(_dev())
-                v = torch.tensor(value[:3], dtype=torch.float64, device=_dev()) / count
-                loads[ix[:, None, None], iy[None, :, None], iz[None, None, :]] = v
+                ix = tuple(torch.from_numpy(sel[d]).to(_dev()).reshape([-1 if k == d else 1 for k in range(N)])
+                           for d in range(N))
+                loads[ix] = torch.tensor(value[:N], dtype=torch.float64, device=_dev()) / count
             else:
                 if count == 0:
                     raise RuntimeError("Dirichlet region unmatched")
-                blk = np.ix_(sel[0], sel[1], sel[2])
-                for c, name in enumerate("xyz"):
+                blk = np.ix_(*sel)
+                for c, name in enumerate("xyz"[:N]):
                     if name not in comps:
                         continue
                     already = mask3[..., c][blk]
@@ -439,7 +713,7 @@ class TensorProductSimulator1_1_1:
 
     def _set_mask(self, mask):
         mask = np.asarray(mask, dtype=bool)
-        if mask.shape != (self.numNodes(), 3):
+        if mask.shape != (self.numNodes(), self.N):
             raise RuntimeError("Size mismatch")
         self._mask = mask.copy()
         self._push_dirichlet()
@@ -449,7 +723,7 @@ class TensorProductSimulator1_1_1:
 
     def _set_dvals(self, values):
         values = np.asarray(values, dtype=np.float64)
-        if values.shape != (self.numNodes(), 3):
+        if values.shape != (self.numNodes(), self.N):
             raise RuntimeError("Size mismatch")
         self._dvals = values.copy()
         self._push_dirichlet()
@@ -465,7 +739,7 @@ class TensorProductSimulator1_1_1:
         return (_to_np(self._loads) != 0)
 
     def setLoads_device(self, f):
-        self._loads = _to_dev(f, (self.numNodes(), 3)).clone()
+        self._loads = _to_dev(f, (self.numNodes(), self.N)).clone()
         self._push_loads()
 
     def buildLoadVector_device(self):
@@ -475,62 +749,104 @@ class TensorProductSimulator1_1_1:
         return _to_np(self._loads)
 
     # ---- operators ----
-    def applyK_device(self, u, variant=0):
-        u = _to_dev(u, (self.numNodes(), 3))
+    def applyK_device(self, u):
+        u = _to_dev(u, (self.numNodes(), self.N))
         out = torch.empty_like(u)
-        _lib.check(self._lib.vfem_sim_apply_k(self._h, _ptr(u), _ptr(out), int(variant), _stream()))
+        _lib.check(self._c("apply_k")(self._h, _ptr(u), _ptr(out), _stream()))
         return out
 
     def applyK(self, u):
         return _to_np(self.applyK_device(u))
 
     def complianceGradient_device(self, u):
-        u = _to_dev(u, (self.numNodes(), 3))
+        u = _to_dev(u, (self.numNodes(), self.N))
         g = torch.empty(self.numElements(), dtype=torch.float64, device=_dev())
-        _lib.check(self._lib.vfem_sim_compliance_gradient(self._h, _ptr(u), _ptr(g), _stream()))
+        _lib.check(self._c("compliance_gradient")(self._h, _ptr(u), _ptr(g), _stream()))
         return g
 
     def _compliance(self, f, u):
         v = ctypes.c_double(0.0)
-        _lib.check(self._lib.vfem_compliance(self._h, _ptr(f), _ptr(u), ctypes.byref(v), _stream()))
+        _lib.check(getattr(self._lib, self._COMPLIANCE)(self._h, _ptr(f), _ptr(u), ctypes.byref(v), _stream()))
         return v.value
 
     def multigridSolver(self, numCoarseningLevels):
-        return MultigridSolver1_1_1(self, int(numCoarseningLevels))
+        return self._MG_CLASS(self, int(numCoarseningLevels))
 
     def _direct_levels(self):
         lv, ne = 0, self._ne.copy()
-        while np.all(ne % 2 == 0) and np.prod(ne + 1) * 3 > 3000 and lv < 12:
+        while np.all(ne % 2 == 0) and np.prod(self.P * ne + 1) * self.N > 3000 and lv < 12:
             ne //= 2
             lv += 1
         return lv
 
-    # TPS::solve's method: "auto" factorises K (band Cholesky, vfem_sim_direct_solve) when its band fits in band.BAND_CAP_BYTES
+    # TPS::solve's method: "auto" factorises K (band Cholesky, <prefix>direct_solve) when its band fits in band.BAND_CAP_BYTES
     # (8 GiB, a fixed cap: the choice depends on the grid only) and runs the multigrid-preconditioned CG stand-in above it;
     # "cholesky" and "pcg" force one of the two
     directSolver = "auto"
 
     def directBandBytes(self):
-        return int(self._lib.vfem_sim_direct_band_bytes(self._h))
+        return int(self._c("direct_band_bytes")(self._h))
 
     def numDirectFactorizations(self):
-        return int(self._lib.vfem_sim_direct_factorizations(self._h))
+        return int(self._c("direct_factorizations")(self._h))
 
     def solve_device(self, f):
         """TPS::solve (TPS.hh:834-865) on the device: u = K^-1 f, 0 at the Dirichlet components.  The band Cholesky factor of K is
         kept until the operator changes, as the reference keeps its CHOLMOD factor; the stand-in is MG-PCG to a relative residual
-        of 1e-11."""
+        of 1e-11 (``_stand_in_solve`` of the two paths)."""
         if np.any(self._dvals[self._mask] != 0):
             raise RuntimeError("Nonzero Dirichlet constraints currently unsupported")
-        f = _to_dev(f, (self.numNodes(), 3))
+        f = _to_dev(f, (self.numNodes(), self.N))
         if _factorize(self.directSolver, self.directBandBytes()):
             u = torch.empty_like(f)
-            _lib.check(self._lib.vfem_sim_direct_solve(self._h, _ptr(f), _ptr(u), _stream()))
+            _lib.check(self._c("direct_solve")(self._h, _ptr(f), _ptr(u), _stream()))
             return u
         mg = getattr(self, "_direct_mg", None)
         if mg is None:
             mg = self.multigridSolver(self._direct_levels())
             self._direct_mg = mg
+        return self._stand_in_solve(mg, f)
+
+    def solve(self, f):
+        return _to_np(self.solve_device(f))
+
+    def solveWithImposedLoads(self):
+        return self.solve(self.buildLoadVector())
+
+
+class TensorProductSimulator1_1_1(_Simulator):
+    """``pyVoxelFEM.detail.TensorProductSimulator1_1_1``: the tuned <1,1,1> path (``vfem_sim_*``)."""
+
+    N, P = 3, 1
+    _SIM_PREFIX = "vfem_sim_"
+    _COMPLIANCE = "vfem_compliance"
+    _MG_CLASS = MultigridSolver1_1_1
+    _GET_DENSITIES_WRITES_STORED = True
+    _GETK_MAX_ELEMENTS = 1 << 21
+
+    def _create(self, out, lo, hi, ne, pad_lo, pad_hi):
+        # the padding of a slab simulator is a one-shot setting that the next vfem_sim_create consumes
+        _lib.check(self._c("set_next_element_padding")(pad_lo, pad_hi))
+        return self._c("create")(out, lo, hi, ne)
+
+    @property
+    def ETensor(self):
+        raise RuntimeError("ETensor objects are not exposed; use readMaterial (isotropic materials)")
+
+    def setUniformDensities(self, density):
+        # filled by the library: no temporary (1 GiB at 512^3); it raises the same range error
+        _lib.check(self._c("set_uniform_density")(self._h, float(density), _stream()))
+
+    def _push_loads(self):
+        _lib.check(self._c("set_loads")(self._h, _ptr(self._loads), _stream()))
+
+    def applyK_device(self, u, variant=0):
+        u = _to_dev(u, (self.numNodes(), 3))
+        out = torch.empty_like(u)
+        _lib.check(self._c("apply_k")(self._h, _ptr(u), _ptr(out), int(variant), _stream()))
+        return out
+
+    def _stand_in_solve(self, mg, f):
         u = mg.preconditionedConjugateGradient_device(torch.zeros((self.numNodes(), 3), dtype=torch.float64,
                                                                   device=_dev()),
                                                       f, 500, 1e-11, None, 1, 2, True)
@@ -540,222 +856,43 @@ class TensorProductSimulator1_1_1:
                                % (mg.last_relative_residual, mg.last_iterations))
         return u
 
-    def solve(self, f):
-        return _to_np(self.solve_device(f))
 
-    def solveWithImposedLoads(self):
-        return self.solve(self.buildLoadVector())
+class _GenericSimulator(_Simulator):
+    """Generic path (``vfem_gsim_*``): TensorProductSimulator<p,..,p> for N = 2, 3 and p = 1, 2 other than the tuned
+    <1,1,1> instantiation -- the 2-D simulators the reference binds (VoxelFEM.cc:226, plane stress) and the degree-2
+    elements its templates support (TPS.hh:97-110)."""
 
+    _SIM_PREFIX = "vfem_gsim_"
+    _COMPLIANCE = "vfem_gsim_compliance"
+    _MG_CLASS = _GenericMultigridSolver
+    _GET_DENSITIES_WRITES_STORED = False
 
-# ----------------------------------------------------------------------------------------------
-# MultigridSolver<1,1,1>
-# ----------------------------------------------------------------------------------------------
+    def _create(self, out, lo, hi, ne, pad_lo, pad_hi):
+        return self._c("create_padded")(out, self.N, self.P, lo, hi, ne, pad_lo, pad_hi)
 
-class _LevelView:
-    """What ``MultigridSolver.getSimulator(l)`` exposes for coarse levels (sizes + Dirichlet mask)."""
-
-    def __init__(self, mg, l):
-        self._mg, self._l = mg, l
-
-    def numNodes(self):
-        return int(self._mg._lib.vfem_mg_level_num_nodes(self._mg._h, self._l))
-
-    def NbElementsPerDimension(self):
-        ne = (ctypes.c_int64 * 3)()
-        _lib.check(self._mg._lib.vfem_mg_level_dims(self._mg._h, self._l, ne))
-        return np.array(list(ne), dtype=np.int64)
-
-    def numElements(self):
-        return int(np.prod(self.NbElementsPerDimension()))
-
-    @property
-    def dirichletMask(self):
-        m = np.empty(self.numNodes(), dtype=np.uint8)
-        _lib.check(self._mg._lib.vfem_mg_level_dirichlet_mask(self._mg._h, self._l, m.ctypes.data_as(ctypes.c_void_p)))
-        return np.stack([(m >> c) & 1 for c in range(3)], axis=1).astype(bool)
-
-
-class MultigridSolver1_1_1:
-    """``pyVoxelFEM.detail.MultigridSolver1_1_1`` (VoxelFEM.cc:94-131; MG.hh:11-759)."""
-
-    def __init__(self, tps, numCoarseningLevels):
-        self._lib = _lib.load()
-        self._tps = tps                      # keeps the fine simulator alive (MG.hh:32,88)
-        h = ctypes.c_void_p()
-        _lib.check(self._lib.vfem_mg_create(ctypes.byref(h), tps._h, int(numCoarseningLevels)))
-        self._h = h
-        self.L = int(numCoarseningLevels)
-        self.buildBlockStiffnessMatrices = True
-        self.buildFinestBlockStiffnessMatrix = False
-        self.last_iterations = 0
-        self.last_relative_residual = 0.0
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                self._lib.vfem_mg_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
-    def _nn(self, l):
-        n = int(self._lib.vfem_mg_level_num_nodes(self._h, int(l)))
-        if n < 0:
-            raise IndexError("vector::_M_range_check")      # m_sims.at(l)
-        return n
-
-    def getSimulator(self, l):
-        self._nn(l)
-        return self._tps if int(l) == 0 else _LevelView(self, int(l))
-
-    def setSymmetricGaussSeidel(self, symmetric):
-        self._lib.vfem_mg_set_symmetric_gauss_seidel(self._h, int(bool(symmetric)))
-
-    def updateElementStiffnessMatrices(self):
-        _lib.check(self._lib.vfem_mg_update_operators(self._h, _stream()))
-
-    def updateBlockKs(self):
-        _lib.check(self._lib.vfem_mg_update_operators(self._h, _stream()))
-
-    # ---- per-operator entry points (device variants first) ----
-    def applyK_device(self, l, u):
-        u = _to_dev(u, (self._nn(l), 3))
-        out = torch.empty_like(u)
-        _lib.check(self._lib.vfem_mg_apply_k(self._h, int(l), _ptr(u), _ptr(out), _stream()))
-        return out
-
-    def applyK(self, l, u):
-        return _to_np(self.applyK_device(l, u))
-
-    def computeResidual_device(self, l, u, b):
-        u = _to_dev(u, (self._nn(l), 3))
-        b = _to_dev(b, (self._nn(l), 3))
-        r = torch.empty_like(u)
-        _lib.check(self._lib.vfem_mg_residual(self._h, int(l), _ptr(u), _ptr(b), _ptr(r), _stream()))
-        return r
-
-    def computeResidual(self, l, u, b):
-        return _to_np(self.computeResidual_device(l, u, b))
-
-    def smoothing_device(self, l, u, b, forward=True):
-        u = _to_dev(u, (self._nn(l), 3)).clone()
-        b = _to_dev(b, (self._nn(l), 3))
-        if u.shape != b.shape:
-            raise RuntimeError("Invalid input size")
-        _lib.check(self._lib.vfem_mg_smooth(self._h, int(l), _ptr(u), _ptr(b), int(bool(forward)), _stream()))
+    def _stand_in_solve(self, mg, f):
+        # a grid with odd element counts cannot be coarsened; beyond the dense-factorisation size it is solved by plain CG
+        plain = mg.L == 0 and self.numNodes() * self.N > 40000
+        u = mg.preconditionedConjugateGradient_device(
+            torch.zeros((self.numNodes(), self.N), dtype=torch.float64, device=_dev()),
+            f, 500000 if plain else 2000, 1e-11, None, 1, 0 if plain else 2, True)
+        if mg.last_relative_residual > 1e-10:
+            raise RuntimeError("direct-solve replacement did not converge (relative residual %g)" % mg.last_relative_residual)
         return u
 
-    def smoothing(self, l, u, b):
-        """Bound as updateElementStiffnessMatrices + one forward sweep on a copy (VoxelFEM.cc:99-104).  The
-        reference binding runs the sequential sweep (MG.hh:269-282); the solver itself uses the multicoloured
-        sweep (MG.hh:336-340), which is what this returns."""
-        self.updateElementStiffnessMatrices()
-        return _to_np(self.smoothing_device(l, u, b, True))
 
-    def zeroOutDirichletComponents(self, l, u):
-        t = _to_dev(u, (self._nn(l), 3)).clone()
-        _lib.check(self._lib.vfem_mg_zero_dirichlet(self._h, int(l), _ptr(t), _stream()))
-        return _to_np(t)
+class TensorProductSimulator1_1(_GenericSimulator):
+    """``pyVoxelFEM.detail.TensorProductSimulator1_1`` (VoxelFEM.cc:226): bilinear quadrilaterals, plane stress."""
+    N, P = 2, 1
 
-    def restriction_device(self, fine_level, values):
-        v = _to_dev(values, (self._nn(fine_level), 3))
-        out = torch.empty((self._nn(fine_level + 1), 3), dtype=torch.float64, device=_dev())
-        _lib.check(self._lib.vfem_mg_restrict(self._h, int(fine_level), _ptr(v), _ptr(out), _stream()))
-        return out
 
-    def interpolation_device(self, fine_level, values, out=None):
-        v = _to_dev(values, (self._nn(fine_level + 1), 3))
-        acc = out is not None
-        if out is None:
-            out = torch.empty((self._nn(fine_level), 3), dtype=torch.float64, device=_dev())
-        _lib.check(self._lib.vfem_mg_interpolate(self._h, int(fine_level), _ptr(v), _ptr(out), int(acc), _stream()))
-        return out
+class TensorProductSimulator2_2(_GenericSimulator):
+    N, P = 2, 2
 
-    def coarsestSolve_device(self, b):
-        b = _to_dev(b, (self._nn(self.L), 3))
-        x = torch.empty_like(b)
-        _lib.check(self._lib.vfem_mg_coarsest_solve(self._h, _ptr(b), _ptr(x), _stream()))
-        return x
 
-    def _field(self, which, l):
-        n = self._nn(l) if which != 2 else self._nn(0)
-        p = self._lib.vfem_mg_field_ptr(self._h, which, int(l))
-        out = torch.empty((n, 3), dtype=torch.float64, device=_dev())
-        _lib.check(self._lib.vfem_copy_d2d(_ptr(out), ctypes.c_void_p(p), n * 3 * 8, _stream()))
-        return out
-
-    def debug_get_x(self, l):
-        return _to_np(self._field(0, l))
-
-    def debug_get_b(self, l):
-        return _to_np(self._field(1, l))
-
-    def debugMulticolorVisit(self):
-        """Visit order of the multicoloured sweep on level 0 (MG.hh:328-334)."""
-        nn = tuple(self._tps._nn)
-        result = np.zeros(nn, dtype=np.int32)
-        counter = 0
-        for lni in range(8):
-            c = ((lni >> 2) & 1, (lni >> 1) & 1, lni & 1)
-            sub = result[c[0]::2, c[1]::2, c[2]::2]
-            sub[...] = counter + np.arange(sub.size).reshape(sub.shape)
-            counter += sub.size
-        return result.reshape(-1)
-
-    # ---- solvers ----
-    def solve_device(self, u, f, numSteps, numSmoothingSteps, stiffnessUpdated=False, zeroDirichlet=False,
-                     it_callback=None, fullMultigrid=False):
-        x = _to_dev(u, (self._nn(0), 3)).clone()
-        f = _to_dev(f, (self._nn(0), 3))
-        if it_callback is None:
-            _lib.check(self._lib.vfem_mg_solve(self._h, _ptr(x), _ptr(f), int(numSteps), int(numSmoothingSteps),
-                                               int(bool(stiffnessUpdated)), int(bool(zeroDirichlet)),
-                                               int(bool(fullMultigrid)), _stream()))
-            return x
-        for i in range(int(numSteps)):
-            _lib.check(self._lib.vfem_mg_solve(self._h, _ptr(x), _ptr(f), 1, int(numSmoothingSteps),
-                                               int(bool(stiffnessUpdated) or i > 0), int(bool(zeroDirichlet)),
-                                               int(bool(fullMultigrid) and i == 0), _stream()))
-            it_callback(i, _to_np(x))
-        return x
-
-    def solve(self, u, f, numSteps, numSmoothingSteps, stiffnessUpdated=False, zeroDirichlet=False,
-              it_callback=None, fullMultigrid=False):
-        return _to_np(self.solve_device(u, f, numSteps, numSmoothingSteps, stiffnessUpdated, zeroDirichlet,
-                                        it_callback, fullMultigrid))
-
-    def preconditionedConjugateGradient_device(self, u, b, maxIter, tol, it_callback=None, mgIterations=1,
-                                               mgSmoothingIterations=1, fullMultigrid=False, residual_cb=None):
-        if isinstance(u, torch.Tensor) and isinstance(b, torch.Tensor) and u.shape != b.shape:
-            raise RuntimeError("x and b should have the same size")
-        x = _to_dev(u).reshape(-1, 3).clone()
-        b = _to_dev(b).reshape(-1, 3)
-        if x.shape[0] != b.shape[0]:
-            raise RuntimeError("x and b should have the same size")
-        if x.shape[0] != self._nn(0):
-            raise RuntimeError("size of input and number of nodes don't correspond")
-        its = ctypes.c_int(0)
-        rel = ctypes.c_double(0.0)
-
-        def _cb(_user, it, rnorm):
-            if residual_cb is not None:
-                residual_cb(it, rnorm)
-            if it_callback is not None:
-                it_callback(it, _to_np(x), _to_np(self._field(2, 0)))
-
-        cb = _lib.RESIDUAL_CB(_cb) if (residual_cb is not None or it_callback is not None) else _lib.RESIDUAL_CB()
-        _lib.check(self._lib.vfem_mg_pcg(self._h, _ptr(x), _ptr(b), int(maxIter), float(tol), int(mgIterations),
-                                         int(mgSmoothingIterations), int(bool(fullMultigrid)), cb, None,
-                                         ctypes.byref(its), ctypes.byref(rel), _stream()))
-        self.last_iterations = its.value
-        self.last_relative_residual = rel.value
-        return x
-
-    def preconditionedConjugateGradient(self, u, b, maxIter, tol, it_callback=None, mgIterations=1,
-                                        mgSmoothingIterations=1, fullMultigrid=False):
-        return _to_np(self.preconditionedConjugateGradient_device(u, b, maxIter, tol, it_callback, mgIterations,
-                                                                  mgSmoothingIterations, fullMultigrid))
+class TensorProductSimulator2_2_2(_GenericSimulator):
+    """27-node hexahedra; supported by the reference templates (TPS.hh:97-110), unbound there (VoxelFEM.cc:226-229)."""
+    N, P = 3, 2
 
 
 # ----------------------------------------------------------------------------------------------
@@ -1165,519 +1302,6 @@ class OCOptimizer1_1_1:
 # ----------------------------------------------------------------------------------------------
 # module-level factories (VoxelFEM.cc:136-216, 234-240)
 # ----------------------------------------------------------------------------------------------
-
-class _GenericSimulator:
-    """Generic path (``libvfem`` ``vfem_gsim_*``): TensorProductSimulator<p,..,p> for N = 2, 3 and p = 1, 2 other than
-    the tuned <1,1,1> instantiation -- the 2-D simulators the reference binds (VoxelFEM.cc:226, plane stress) and
-    the degree-2 elements its templates support (TPS.hh:97-110).  Same surface as ``TensorProductSimulator1_1_1``."""
-
-    N = 3
-    P = 1
-
-    def __init__(self, domainBoundingBox, numElemg, _element_padding=(0, 0)):
-        """``_element_padding`` (slab decomposition, ndr_amd/distributed_q2.py): element layers kept below / above the node
-        grid along x in the density array only (``setElementDensities_padded``)"""
-        _lib.require_gpu()
-        self._lib = _lib.load()
-        N, p = self.N, self.P
-        lo = np.asarray(domainBoundingBox[0], dtype=np.float64).reshape(-1)
-        hi = np.asarray(domainBoundingBox[1], dtype=np.float64).reshape(-1)
-        ne = [int(v) for v in numElemg]
-        if len(ne) != N or lo.size != N or hi.size != N:
-            raise RuntimeError("Dimension mismatch: %d vs %d" % (len(ne), N))
-        self._bbmin, self._bbmax = lo.copy(), hi.copy()
-        self._ne = np.array(ne, dtype=np.int64)
-        self._nn = p * self._ne + 1
-        h = ctypes.c_void_p()
-        self._pad = (int(_element_padding[0]), int(_element_padding[1]))
-        _lib.check(self._lib.vfem_gsim_create_padded(
-            ctypes.byref(h), N, p, lo.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-            hi.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), self._ne.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-            self._pad[0], self._pad[1]))
-        self._h = h
-        self._E0, self._Emin, self._gamma = 1.0, 1e-9, 3.0           # TPS.hh:1392-1394
-        self._mask = np.zeros((self.numNodes(), N), dtype=bool)
-        self._dvals = np.zeros((self.numNodes(), N))
-        self._loads = torch.zeros((self.numNodes(), N), dtype=torch.float64, device=_dev())
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                self._lib.vfem_gsim_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
-    # ---- sizes / geometry ----
-    def numNodes(self):
-        return int(np.prod(self._nn))
-
-    def numElements(self):
-        return int(np.prod(self._ne))
-
-    def NbElementsPerDimension(self):
-        return self._ne.copy()
-
-    def nodePosition(self, ni):
-        idx = np.array(np.unravel_index(int(ni), tuple(self._nn)), dtype=np.float64)
-        return self._bbmin + idx * (self._bbmax - self._bbmin) / (self._nn - 1.0)
-
-    def elementIndexForGridCell(self, cellIdxs):
-        return int(np.ravel_multi_index(tuple(int(c) for c in cellIdxs), tuple(self._ne)))
-
-    def elementNodes(self, ei):
-        e = np.array(np.unravel_index(int(ei), tuple(self._ne)))
-        out = []
-        for loc in np.ndindex(*([self.P + 1] * self.N)):
-            out.append(int(np.ravel_multi_index(tuple(self.P * e + np.array(loc)), tuple(self._nn))))
-        return np.array(out, dtype=np.uint64)
-
-    def elemNodeGlobalIndex(self, ei, n):
-        return int(self.elementNodes(ei)[int(n)])
-
-    def getMesh(self):
-        """(V, F): all node positions; per element its corner nodes in Gmsh quad / hexahedron order (TPS.hh:531-565)"""
-        N, p = self.N, self.P
-        idx = np.stack(np.meshgrid(*[np.arange(n) for n in self._nn], indexing="ij"), -1).reshape(-1, N)
-        V = self._bbmin + idx * (self._bbmax - self._bbmin) / (self._nn - 1.0)
-        eidx = np.stack(np.meshgrid(*[np.arange(n) for n in self._ne], indexing="ij"), -1).reshape(-1, N)
-        nstr = np.array([int(np.prod(self._nn[d + 1:])) for d in range(N)])
-        first = (p * eidx) @ nstr
-        corners = [(0, 0), (1, 0), (1, 1), (0, 1)] if N == 2 else \
-            [(0, 0, 0), (0, 0, 1), (0, 1, 1), (0, 1, 0), (1, 0, 0), (1, 0, 1), (1, 1, 1), (1, 1, 0)]
-        F = np.stack([first + (p * np.array(c)) @ nstr for c in corners], axis=1)
-        return V, F
-
-    # ---- material / SIMP ----
-    def readMaterial(self, materialPath):
-        young, poisson = _read_isotropic_material(materialPath)
-        self._young, self._poisson = young, poisson
-        _lib.check(self._lib.vfem_gsim_set_isotropic(self._h, young, poisson))
-        self._direct_mg = None                    # the reference resets its solver when the operator changes (TPS.hh:404)
-
-    def _lame(self):
-        """ElasticityTensor::setIsotropic (ElasticityTensor.hh:100-133): 3-D Lame parameters, plane stress in 2-D"""
-        E, nu = getattr(self, "_young", 1.0), getattr(self, "_poisson", 0.0)
-        lam = nu * E / ((1.0 + nu) * (1.0 - 2.0 * nu)) if self.N == 3 else nu * E / (1.0 - nu * nu)
-        return lam, E / (2.0 + 2.0 * nu)
-
-    def readDensities(self, materialPath, fieldName="density"):
-        """TPS::readDensities (VoxelFEM.cc:54)"""
-        self.setElementDensities(_densities_from_msh(materialPath, fieldName, self._ne, self.N))
-
-    def constantStrainLoad(self, eps):
-        """TPS::constantStrainLoad (VoxelFEM.cc:66), evaluated on the device"""
-        lam, mu = self._lame()
-        rho = self.getDensities_device().reshape(tuple(int(n) for n in self._ne))
-        return _to_np(_constant_strain_load(eps, lam, mu, (self._bbmax - self._bbmin) / self._ne, self.P, rho))
-
-    def getK(self):
-        """TPS::getK (VoxelFEM.cc:62): assembled stiffness matrix, upper triangle, compressed columns (host, small grids)"""
-        if self.numElements() * (self.P + 1) ** (2 * self.N) > (1 << 30):
-            raise RuntimeError("getK assembles on the host; use applyK for grids of this size")
-        rho = self.getDensities()
-        young = self._Emin + rho ** self._gamma * (self._E0 - self._Emin)
-        nodes = np.stack([np.asarray(self.elementNodes(e), dtype=np.int64) for e in range(self.numElements())])
-        return _assemble_upper(nodes, self.fullDensityElementStiffnessMatrix(), young, self.N, self.numNodes())
-
-    def _push_simp(self):
-        _lib.check(self._lib.vfem_gsim_set_simp(self._h, self._E0, self._Emin, self._gamma))
-
-    E_0 = property(lambda s: s._E0, lambda s, v: (setattr(s, "_E0", float(v)), s._push_simp())[0])
-    E_min = property(lambda s: s._Emin, lambda s, v: (setattr(s, "_Emin", float(v)), s._push_simp())[0])
-    gamma = property(lambda s: s._gamma, lambda s, v: (setattr(s, "_gamma", float(v)), s._push_simp())[0])
-
-    def fullDensityElementStiffnessMatrix(self):
-        ke = int(self._lib.vfem_gsim_ke_size(self._h))
-        K0 = np.empty((ke, ke))
-        _lib.check(self._lib.vfem_gsim_k0(self._h, K0.ctypes.data_as(ctypes.c_void_p)))
-        return K0
-
-    def elementStiffnessMatrix(self, ei):
-        rho = self.elementDensity(ei)
-        return (self._Emin + rho ** self._gamma * (self._E0 - self._Emin)) * self.fullDensityElementStiffnessMatrix()
-
-    def clearCachedElementStiffness(self):
-        pass
-
-    # ---- densities ----
-    def setElementDensities(self, rho):
-        if self._pad != (0, 0):
-            raise RuntimeError("this simulator stores padding element layers: use setElementDensities_padded")
-        t = _to_dev(rho, (self.numElements(),))
-        _lib.check(self._lib.vfem_gsim_set_densities(self._h, _ptr(t), _stream()))
-
-    def setElementDensities_padded(self, rho):
-        """all stored element layers (padding below, the node grid's elements, padding above), x slowest"""
-        t = _to_dev(rho, (int(self._lib.vfem_gsim_num_stored_elements(self._h)),))
-        _lib.check(self._lib.vfem_gsim_set_densities(self._h, _ptr(t), _stream()))
-
-    def setUniformDensities(self, density):
-        if density > 1.0 or density < 0:
-            raise RuntimeError("Density value (%f) has to be in between 0 and 1" % density)
-        n = int(self._lib.vfem_gsim_num_stored_elements(self._h))
-        self.setElementDensities_padded(torch.full((n,), float(density), dtype=torch.float64, device=_dev()))
-
-    def getDensities_device(self):
-        t = torch.empty(self.numElements(), dtype=torch.float64, device=_dev())
-        _lib.check(self._lib.vfem_gsim_get_densities(self._h, _ptr(t), _stream()))
-        return t
-
-    def getDensities(self):
-        return _to_np(self.getDensities_device())
-
-    def setElementDensity(self, ei, value):
-        t = self.getDensities_device()
-        t[int(ei)] = float(value)
-        self.setElementDensities(t)
-
-    def elementDensity(self, ei):
-        return float(self.getDensities_device()[int(ei)].item())
-
-    # ---- boundary conditions ----
-    def _push_dirichlet(self):
-        m = np.zeros(self.numNodes(), dtype=np.uint8)
-        for c in range(self.N):
-            m |= self._mask[:, c].astype(np.uint8) << c
-        vals = np.ascontiguousarray(self._dvals)
-        _lib.check(self._lib.vfem_gsim_set_dirichlet(self._h, m.ctypes.data_as(ctypes.c_void_p),
-                                                    vals.ctypes.data_as(ctypes.c_void_p)))
-        self._direct_mg = None                    # coarse Dirichlet masks of a cached hierarchy would be stale (TPS.hh:404)
-
-    def applyDisplacementsAndLoadsFromFile(self, bcPath):
-        """applyDisplacementsAndLoads (TPS.hh:358-409), see ``TensorProductSimulator1_1_1``."""
-        N = self.N
-        size = self._bbmax - self._bbmin
-        spacing = size / (self._nn - 1.0)
-        coords = [self._bbmin[d] + np.arange(self._nn[d]) * spacing[d] for d in range(N)]
-        shape = tuple(self._nn)
-        mask3 = self._mask.reshape(shape + (N,))
-        vals3 = self._dvals.reshape(shape + (N,))
-        loads = np.zeros(shape + (N,))
-        loads[...] = _to_np(self._loads).reshape(shape + (N,))
-        for kind, comps, value, lo, hi, relative in _parse_regions(bcPath):
-            lo, hi = np.array(lo[:N]), np.array(hi[:N])
-            if relative:
-                lo, hi = self._bbmin + lo * size, self._bbmin + hi * size
-            sel = [np.flatnonzero((coords[d] >= lo[d]) & (coords[d] <= hi[d])) for d in range(N)]
-            count = int(np.prod([s.size for s in sel]))
-            blk = np.ix_(*sel)
-            if kind == "force":
-                if count == 0:
-                    raise RuntimeError("Force constraint region unmatched")
-                for c in range(N):
-                    loads[..., c][blk] = value[c] / count
-            else:
-                if count == 0:
-                    raise RuntimeError("Dirichlet region unmatched")
-                for c, name in enumerate("xyz"[:N]):
-                    if name not in comps:
-                        continue
-                    already = mask3[..., c][blk]
-                    if np.any(already & (np.abs(vals3[..., c][blk] - value[c]) > 1e-10)):
-                        raise RuntimeError("Conflicting dirichlet displacements.")
-                    vc = vals3[..., c]
-                    mc = mask3[..., c]
-                    vc[blk] = np.where(already, vc[blk], value[c])
-                    mc[blk] = True
-        self._loads = _to_dev(loads.reshape(-1, N))
-        self._push_dirichlet()
-
-    def _get_mask(self):
-        return self._mask.copy()
-
-    def _set_mask(self, mask):
-        mask = np.asarray(mask, dtype=bool)
-        if mask.shape != (self.numNodes(), self.N):
-            raise RuntimeError("Size mismatch")
-        self._mask = mask.copy()
-        self._push_dirichlet()
-
-    def _get_dvals(self):
-        return self._dvals.copy()
-
-    def _set_dvals(self, values):
-        values = np.asarray(values, dtype=np.float64)
-        if values.shape != (self.numNodes(), self.N):
-            raise RuntimeError("Size mismatch")
-        self._dvals = values.copy()
-        self._push_dirichlet()
-
-    dirichletMask = property(_get_mask, _set_mask)
-    dirichletValues = property(_get_dvals, _set_dvals)
-
-    def getDirichletVarsAndValues(self):
-        idx = np.flatnonzero(self._mask.reshape(-1))
-        return list(idx), list(self._dvals.reshape(-1)[idx])
-
-    def getForceMask(self):
-        return (_to_np(self._loads) != 0)
-
-    def setLoads_device(self, f):
-        self._loads = _to_dev(f, (self.numNodes(), self.N)).clone()
-
-    def buildLoadVector_device(self):
-        return self._loads.clone()
-
-    def buildLoadVector(self):
-        return _to_np(self._loads)
-
-    # ---- operators ----
-    def applyK_device(self, u):
-        u = _to_dev(u, (self.numNodes(), self.N))
-        out = torch.empty_like(u)
-        _lib.check(self._lib.vfem_gsim_apply_k(self._h, _ptr(u), _ptr(out), _stream()))
-        return out
-
-    def applyK(self, u):
-        return _to_np(self.applyK_device(u))
-
-    def complianceGradient_device(self, u):
-        u = _to_dev(u, (self.numNodes(), self.N))
-        g = torch.empty(self.numElements(), dtype=torch.float64, device=_dev())
-        _lib.check(self._lib.vfem_gsim_compliance_gradient(self._h, _ptr(u), _ptr(g), _stream()))
-        return g
-
-    def _compliance(self, f, u):
-        v = ctypes.c_double(0.0)
-        _lib.check(self._lib.vfem_gsim_compliance(self._h, _ptr(f), _ptr(u), ctypes.byref(v), _stream()))
-        return v.value
-
-    def multigridSolver(self, numCoarseningLevels):
-        return _GenericMultigridSolver(self, int(numCoarseningLevels))
-
-    def _direct_levels(self):
-        lv, ne = 0, self._ne.copy()
-        while np.all(ne % 2 == 0) and np.prod(self.P * ne + 1) * self.N > 3000 and lv < 12:
-            ne //= 2
-            lv += 1
-        return lv
-
-    directSolver = "auto"        # as TensorProductSimulator1_1_1.directSolver
-
-    def directBandBytes(self):
-        return int(self._lib.vfem_gsim_direct_band_bytes(self._h))
-
-    def numDirectFactorizations(self):
-        return int(self._lib.vfem_gsim_direct_factorizations(self._h))
-
-    def solve_device(self, f):
-        """TPS::solve (TPS.hh:834-865) on the device, see ``TensorProductSimulator1_1_1.solve_device``.  The stand-in is MG-PCG to
-        1e-11 (plain CG on grids that cannot be coarsened)."""
-        if np.any(self._dvals[self._mask] != 0):
-            raise RuntimeError("Nonzero Dirichlet constraints currently unsupported")
-        f = _to_dev(f, (self.numNodes(), self.N))
-        if _factorize(self.directSolver, self.directBandBytes()):
-            u = torch.empty_like(f)
-            _lib.check(self._lib.vfem_gsim_direct_solve(self._h, _ptr(f), _ptr(u), _stream()))
-            return u
-        mg = getattr(self, "_direct_mg", None)
-        if mg is None:
-            mg = self.multigridSolver(self._direct_levels())
-            self._direct_mg = mg
-        # a grid with odd element counts cannot be coarsened; beyond the dense-factorisation size it is solved by plain CG
-        plain = mg.L == 0 and self.numNodes() * self.N > 40000
-        u = mg.preconditionedConjugateGradient_device(
-            torch.zeros((self.numNodes(), self.N), dtype=torch.float64, device=_dev()),
-            f, 500000 if plain else 2000, 1e-11, None, 1, 0 if plain else 2, True)
-        if mg.last_relative_residual > 1e-10:
-            raise RuntimeError("direct-solve replacement did not converge (relative residual %g)" % mg.last_relative_residual)
-        return u
-
-    def solve(self, f):
-        return _to_np(self.solve_device(f))
-
-    def solveWithImposedLoads(self):
-        return self.solve(self.buildLoadVector())
-
-
-class TensorProductSimulator1_1(_GenericSimulator):
-    """``pyVoxelFEM.detail.TensorProductSimulator1_1`` (VoxelFEM.cc:226): bilinear quadrilaterals, plane stress."""
-    N, P = 2, 1
-
-
-class TensorProductSimulator2_2(_GenericSimulator):
-    N, P = 2, 2
-
-
-class TensorProductSimulator2_2_2(_GenericSimulator):
-    """27-node hexahedra; supported by the reference templates (TPS.hh:97-110), unbound there (VoxelFEM.cc:226-229)."""
-    N, P = 3, 2
-
-
-class _GenericLevelView:
-    def __init__(self, mg, l):
-        self._mg, self._l = mg, l
-
-    def numNodes(self):
-        return self._mg._nn(self._l)
-
-    def NbElementsPerDimension(self):
-        ne = (ctypes.c_int64 * 3)()
-        _lib.check(self._mg._lib.vfem_gmg_level_dims(self._mg._h, self._l, ne))
-        return np.array(list(ne)[:self._mg.N], dtype=np.int64)
-
-    def numElements(self):
-        return int(np.prod(self.NbElementsPerDimension()))
-
-    @property
-    def dirichletMask(self):
-        m = np.empty(self.numNodes(), dtype=np.uint8)
-        _lib.check(self._mg._lib.vfem_gmg_level_dirichlet_mask(self._mg._h, self._l, m.ctypes.data_as(ctypes.c_void_p)))
-        return np.stack([(m >> c) & 1 for c in range(self._mg.N)], axis=1).astype(bool)
-
-
-class _GenericMultigridSolver:
-    """MultigridSolver<p,..,p> on the generic path (MG.hh); same surface as ``MultigridSolver1_1_1``."""
-
-    def __init__(self, tps, numCoarseningLevels):
-        self._lib = _lib.load()
-        self._tps = tps
-        self.N = tps.N
-        h = ctypes.c_void_p()
-        _lib.check(self._lib.vfem_gmg_create(ctypes.byref(h), tps._h, int(numCoarseningLevels)))
-        self._h = h
-        self.L = int(numCoarseningLevels)
-        self.buildBlockStiffnessMatrices = True
-        self.buildFinestBlockStiffnessMatrix = False
-        self.last_iterations = 0
-        self.last_relative_residual = 0.0
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                self._lib.vfem_gmg_destroy(h)
-            except Exception:
-                pass
-            self._h = None
-
-    def _nn(self, l):
-        n = int(self._lib.vfem_gmg_level_num_nodes(self._h, int(l)))
-        if n < 0:
-            raise IndexError("vector::_M_range_check")
-        return n
-
-    def getSimulator(self, l):
-        self._nn(l)
-        return self._tps if int(l) == 0 else _GenericLevelView(self, int(l))
-
-    def setSymmetricGaussSeidel(self, symmetric):
-        self._lib.vfem_gmg_set_symmetric_gauss_seidel(self._h, int(bool(symmetric)))
-
-    def updateElementStiffnessMatrices(self):
-        _lib.check(self._lib.vfem_gmg_update_operators(self._h, _stream()))
-
-    updateBlockKs = updateElementStiffnessMatrices
-
-    def applyK_device(self, l, u):
-        u = _to_dev(u, (self._nn(l), self.N))
-        out = torch.empty_like(u)
-        _lib.check(self._lib.vfem_gmg_apply_k(self._h, int(l), _ptr(u), _ptr(out), _stream()))
-        return out
-
-    def applyK(self, l, u):
-        return _to_np(self.applyK_device(l, u))
-
-    def computeResidual_device(self, l, u, b):
-        u = _to_dev(u, (self._nn(l), self.N))
-        b = _to_dev(b, (self._nn(l), self.N))
-        r = torch.empty_like(u)
-        _lib.check(self._lib.vfem_gmg_residual(self._h, int(l), _ptr(u), _ptr(b), _ptr(r), _stream()))
-        return r
-
-    def computeResidual(self, l, u, b):
-        return _to_np(self.computeResidual_device(l, u, b))
-
-    def smoothing_device(self, l, u, b, forward=True):
-        u = _to_dev(u, (self._nn(l), self.N)).clone()
-        b = _to_dev(b, (self._nn(l), self.N))
-        _lib.check(self._lib.vfem_gmg_smooth(self._h, int(l), _ptr(u), _ptr(b), int(bool(forward)), _stream()))
-        return u
-
-    def smoothing(self, l, u, b):
-        self.updateElementStiffnessMatrices()
-        return _to_np(self.smoothing_device(l, u, b, True))
-
-    def zeroOutDirichletComponents(self, l, u):
-        t = _to_dev(u, (self._nn(l), self.N)).clone()
-        _lib.check(self._lib.vfem_gmg_zero_dirichlet(self._h, int(l), _ptr(t), _stream()))
-        return _to_np(t)
-
-    def restriction_device(self, fine_level, values):
-        v = _to_dev(values, (self._nn(fine_level), self.N))
-        out = torch.empty((self._nn(fine_level + 1), self.N), dtype=torch.float64, device=_dev())
-        _lib.check(self._lib.vfem_gmg_restrict(self._h, int(fine_level), _ptr(v), _ptr(out), _stream()))
-        return out
-
-    def interpolation_device(self, fine_level, values, out=None):
-        v = _to_dev(values, (self._nn(fine_level + 1), self.N))
-        acc = out is not None
-        if out is None:
-            out = torch.empty((self._nn(fine_level), self.N), dtype=torch.float64, device=_dev())
-        _lib.check(self._lib.vfem_gmg_interpolate(self._h, int(fine_level), _ptr(v), _ptr(out), int(acc), _stream()))
-        return out
-
-    def debugMulticolorVisit(self):
-        """Visit order of the multicoloured sweep on level 0 (MG.hh:285-334)."""
-        nn, p, N = tuple(self._tps._nn), self._tps.P, self.N
-        result = np.zeros(nn, dtype=np.int32)
-        counter = 0
-        for lni in np.ndindex(*([p + 1] * N)):
-            sl = tuple(slice(lni[d], None, (2 if lni[d] in (0, p) else 1) * p) for d in range(N))
-            sub = result[sl]
-            sub[...] = counter + np.arange(sub.size).reshape(sub.shape)
-            counter += sub.size
-        return result.reshape(-1)
-
-    def solve_device(self, u, f, numSteps, numSmoothingSteps, stiffnessUpdated=False, zeroDirichlet=False,
-                     it_callback=None, fullMultigrid=False):
-        x = _to_dev(u, (self._nn(0), self.N)).clone()
-        f = _to_dev(f, (self._nn(0), self.N))
-        steps = [(int(numSteps), bool(stiffnessUpdated), bool(fullMultigrid))] if it_callback is None else \
-            [(1, bool(stiffnessUpdated) or i > 0, bool(fullMultigrid) and i == 0) for i in range(int(numSteps))]
-        for i, (n, upd, fmg) in enumerate(steps):
-            _lib.check(self._lib.vfem_gmg_solve(self._h, _ptr(x), _ptr(f), n, int(numSmoothingSteps), int(upd),
-                                                int(bool(zeroDirichlet)), int(fmg), _stream()))
-            if it_callback is not None:
-                it_callback(i, _to_np(x))
-        return x
-
-    def solve(self, u, f, numSteps, numSmoothingSteps, stiffnessUpdated=False, zeroDirichlet=False,
-              it_callback=None, fullMultigrid=False):
-        return _to_np(self.solve_device(u, f, numSteps, numSmoothingSteps, stiffnessUpdated, zeroDirichlet,
-                                        it_callback, fullMultigrid))
-
-    def preconditionedConjugateGradient_device(self, u, b, maxIter, tol, it_callback=None, mgIterations=1,
-                                               mgSmoothingIterations=1, fullMultigrid=False, residual_cb=None):
-        x = _to_dev(u).reshape(-1, self.N).clone()
-        b = _to_dev(b).reshape(-1, self.N)
-        if x.shape[0] != b.shape[0]:
-            raise RuntimeError("x and b should have the same size")
-        if x.shape[0] != self._nn(0):
-            raise RuntimeError("size of input and number of nodes don't correspond")
-        its, rel = ctypes.c_int(0), ctypes.c_double(0.0)
-
-        def _cb(_user, it, rnorm):
-            if residual_cb is not None:
-                residual_cb(it, rnorm)
-            if it_callback is not None:
-                it_callback(it, _to_np(x), None)
-
-        cb = _lib.RESIDUAL_CB(_cb) if (residual_cb is not None or it_callback is not None) else _lib.RESIDUAL_CB()
-        _lib.check(self._lib.vfem_gmg_pcg(self._h, _ptr(x), _ptr(b), int(maxIter), float(tol), int(mgIterations),
-                                          int(mgSmoothingIterations), int(bool(fullMultigrid)), cb, None,
-                                          ctypes.byref(its), ctypes.byref(rel), _stream()))
-        self.last_iterations = its.value
-        self.last_relative_residual = rel.value
-        return x
-
-    def preconditionedConjugateGradient(self, u, b, maxIter, tol, it_callback=None, mgIterations=1,
-                                        mgSmoothingIterations=1, fullMultigrid=False):
-        return _to_np(self.preconditionedConjugateGradient_device(u, b, maxIter, tol, it_callback, mgIterations,
-                                                                  mgSmoothingIterations, fullMultigrid))
-
 
 def TensorProductSimulator(degreesPerDimension, domainBBox, elementsPerDimension):
     """VoxelFEM.cc:234-240 (+ the degree-2 instantiations the reference leaves commented out, :227,229)"""

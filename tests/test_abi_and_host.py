@@ -162,3 +162,152 @@ def test_host_helpers_of_getk_constant_strain_load_read_densities(tmp_path):
     assert np.array_equal(pv._densities_from_msh(path, "density", ne, 3), rho)
     with pytest.raises(RuntimeError):
         pv._densities_from_msh(str(tmp_path / "field.obj"), "density", ne, 3)
+
+
+# Public surface of the single-GPU binding classes (names without a leading underscore; inspect.signature of the callables, the
+# kind of everything else), recorded before the simulators and the multigrid solvers were folded onto one base class each.
+_SIM_SURFACE = {"E_0": "property",
+ "E_min": "property",
+ "N": "int",
+ "NbElementsPerDimension": "(self)",
+ "P": "int",
+ "applyDisplacementsAndLoadsFromFile": "(self, bcPath)",
+ "applyK": "(self, u)",
+ "applyK_device": "(self, u)",
+ "buildLoadVector": "(self)",
+ "buildLoadVector_device": "(self)",
+ "clearCachedElementStiffness": "(self)",
+ "complianceGradient_device": "(self, u)",
+ "constantStrainLoad": "(self, eps)",
+ "directBandBytes": "(self)",
+ "directSolver": "str",
+ "dirichletMask": "property",
+ "dirichletValues": "property",
+ "elemNodeGlobalIndex": "(self, ei, n)",
+ "elementDensity": "(self, ei)",
+ "elementIndexForGridCell": "(self, cellIdxs)",
+ "elementNodes": "(self, ei)",
+ "elementStiffnessMatrix": "(self, ei)",
+ "fullDensityElementStiffnessMatrix": "(self)",
+ "gamma": "property",
+ "getDensities": "(self)",
+ "getDensities_device": "(self)",
+ "getDirichletVarsAndValues": "(self)",
+ "getForceMask": "(self)",
+ "getK": "(self)",
+ "getMesh": "(self)",
+ "multigridSolver": "(self, numCoarseningLevels)",
+ "nodePosition": "(self, ni)",
+ "numDirectFactorizations": "(self)",
+ "numElements": "(self)",
+ "numNodes": "(self)",
+ "readDensities": "(self, materialPath, fieldName='density')",
+ "readMaterial": "(self, materialPath)",
+ "setElementDensities": "(self, rho)",
+ "setElementDensities_padded": "(self, rho)",
+ "setElementDensity": "(self, ei, value)",
+ "setLoads_device": "(self, f)",
+ "setUniformDensities": "(self, density)",
+ "solve": "(self, f)",
+ "solveWithImposedLoads": "(self)",
+ "solve_device": "(self, f)"}
+_MG_SURFACE = {"applyK": "(self, l, u)",
+ "applyK_device": "(self, l, u)",
+ "computeResidual": "(self, l, u, b)",
+ "computeResidual_device": "(self, l, u, b)",
+ "debugMulticolorVisit": "(self)",
+ "getSimulator": "(self, l)",
+ "interpolation_device": "(self, fine_level, values, out=None)",
+ "preconditionedConjugateGradient": "(self, u, b, maxIter, tol, it_callback=None, mgIterations=1, mgSmoothingIterations=1, "
+                                    "fullMultigrid=False)",
+ "preconditionedConjugateGradient_device": "(self, u, b, maxIter, tol, it_callback=None, mgIterations=1, "
+                                           "mgSmoothingIterations=1, fullMultigrid=False, residual_cb=None)",
+ "restriction_device": "(self, fine_level, values)",
+ "setSymmetricGaussSeidel": "(self, symmetric)",
+ "smoothing": "(self, l, u, b)",
+ "smoothing_device": "(self, l, u, b, forward=True)",
+ "solve": "(self, u, f, numSteps, numSmoothingSteps, stiffnessUpdated=False, zeroDirichlet=False, it_callback=None, "
+          "fullMultigrid=False)",
+ "solve_device": "(self, u, f, numSteps, numSmoothingSteps, stiffnessUpdated=False, zeroDirichlet=False, it_callback=None, "
+                 "fullMultigrid=False)",
+ "updateBlockKs": "(self)",
+ "updateElementStiffnessMatrices": "(self)",
+ "zeroOutDirichletComponents": "(self, l, u)"}
+_VIEW_SURFACE = {"NbElementsPerDimension": "(self)", "dirichletMask": "property", "numElements": "(self)", "numNodes": "(self)"}
+_SIM_TUNED_ONLY = {"ETensor": "property", "applyK_device": "(self, u, variant=0)"}
+_MG_TUNED_ONLY = {"coarsestSolve_device": "(self, b)", "debug_get_b": "(self, l)", "debug_get_x": "(self, l)"}
+
+
+def _surface(cls):
+    import inspect
+    out = {}
+    for name in dir(cls):
+        if not name.startswith("_"):
+            a = inspect.getattr_static(cls, name)
+            out[name] = str(inspect.signature(a)) if callable(a) else type(a).__name__
+    return out
+
+
+def _helper_arguments(cls, helper):
+    """string arguments of the ``_c("...")`` / ``_mg("...")`` calls in the methods ``cls`` ends up with (overrides win)"""
+    import inspect
+    names = set()
+    for attr in dir(cls):
+        a = inspect.getattr_static(cls, attr)
+        for f in ([a.fget, a.fset] if isinstance(a, property) else [a]):
+            if inspect.isfunction(f):
+                names.update(re.findall(r"\._%s\(\"(\w+)\"\)" % helper, inspect.getsource(f)))
+    return names
+
+
+def test_binding_classes_keep_their_surface_and_resolve_only_declared_c_names():
+    import inspect
+    from ndr_amd import _lib
+    from ndr_amd import pyVoxelFEM as pv
+    # the tuned simulator gained P (the shared code is parameterised by it) and the _element_padding argument of the generic one
+    tuned = dict(_SIM_SURFACE, **_SIM_TUNED_ONLY)
+    assert _surface(pv.TensorProductSimulator1_1_1) == tuned
+    for cls in (pv.TensorProductSimulator1_1, pv.TensorProductSimulator2_2, pv.TensorProductSimulator2_2_2):
+        assert _surface(cls) == _SIM_SURFACE, cls
+    for cls in (pv.TensorProductSimulator1_1_1, pv.TensorProductSimulator1_1, pv.TensorProductSimulator2_2, pv.TensorProductSimulator2_2_2):
+        assert str(inspect.signature(cls.__init__)) == "(self, domainBoundingBox, numElemg, _element_padding=(0, 0))"
+    assert (pv.TensorProductSimulator1_1_1.N, pv.TensorProductSimulator1_1_1.P) == (3, 1)
+    assert [(c.N, c.P) for c in (pv.TensorProductSimulator1_1, pv.TensorProductSimulator2_2, pv.TensorProductSimulator2_2_2)] == \
+        [(2, 1), (2, 2), (3, 2)]
+    generic_mg = pv.TensorProductSimulator2_2_2._MG_CLASS
+    assert pv.TensorProductSimulator1_1_1._MG_CLASS is pv.MultigridSolver1_1_1 is pv.detail.MultigridSolver1_1_1
+    assert _surface(pv.MultigridSolver1_1_1) == dict(_MG_SURFACE, **_MG_TUNED_ONLY)
+    assert _surface(generic_mg) == _MG_SURFACE
+    for cls in (pv.MultigridSolver1_1_1, generic_mg):
+        assert str(inspect.signature(cls.__init__)) == "(self, tps, numCoarseningLevels)"
+    assert _surface(pv._LevelView) == _VIEW_SURFACE
+    assert str(inspect.signature(pv._LevelView.__init__)) == "(self, mg, l)"
+
+    # every C name the prefix helpers can build is declared: a name put together from strings fails only when it is called
+    generic_sim = type("G111", (pv._GenericSimulator,), {"N": 3, "P": 1})
+    for cls in (pv.TensorProductSimulator1_1_1, generic_sim, pv.TensorProductSimulator2_2):
+        args = _helper_arguments(cls, "c")
+        assert {"destroy", "set_densities", "get_densities", "apply_k"} <= args, sorted(args)      # the scan sees the methods
+        for name in args:
+            assert cls._SIM_PREFIX + name in _lib.SIGNATURES, (cls.__name__, name)
+        assert cls._COMPLIANCE in _lib.SIGNATURES
+    view_args = _helper_arguments(pv._LevelView, "mg")
+    assert view_args == {"level_dims", "level_dirichlet_mask"}
+    for cls in (pv.MultigridSolver1_1_1, generic_mg):
+        args = _helper_arguments(cls, "mg")
+        assert {"create", "destroy", "solve", "pcg"} <= args, sorted(args)
+        for name in args | view_args:
+            assert cls._MG_PREFIX + name in _lib.SIGNATURES, (cls.__name__, name)
+    assert (pv.TensorProductSimulator1_1_1._SIM_PREFIX, pv._GenericSimulator._SIM_PREFIX) == ("vfem_sim_", "vfem_gsim_")
+    assert (pv.MultigridSolver1_1_1._MG_PREFIX, generic_mg._MG_PREFIX) == ("vfem_mg_", "vfem_gmg_")
+    # the helpers are only ever called with a literal, so the scan above sees every name
+    src = open(os.path.join(ROOT, "ndr_amd", "pyVoxelFEM.py")).read()
+    assert len(re.findall(r"\._c\(", src)) == len(re.findall(r"\._c\(\"\w+\"\)", src))
+    assert len(re.findall(r"\._mg\(", src)) == len(re.findall(r"\._mg\(\"\w+\"\)", src))
+    # users of the simulators' helper outside the module: the slab operator holds a tuned simulator, the knobs take either
+    for path, prefixes in (("ndr_amd/distributed.py", ("vfem_sim_",)), ("tools/_knobs.py", ("vfem_sim_", "vfem_gsim_"))):
+        names = re.findall(r"\._c\(\"(\w+)\"\)", open(os.path.join(ROOT, path)).read())
+        assert names, path
+        for name in names:
+            for prefix in prefixes:
+                assert prefix + name in _lib.SIGNATURES, (path, prefix + name)

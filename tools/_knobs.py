@@ -13,7 +13,5 @@ def set_knob(sim, key, value):
         if not hasattr(lib, "vfem_debug_set"):
             raise SystemExit("key %d is a timing ablation: build `make -C ndr_amd/csrc ablation` and set VFEM_LIB" % key)
         lib.vfem_debug_set(key, value)
-    elif key == 6:
-        _lib.check(lib.vfem_gsim_set_option(sim._h, key, value))
     else:
-        _lib.check(lib.vfem_sim_set_option(sim._h, key, value))
+        _lib.check(sim._c("set_option")(sim._h, key, value))
