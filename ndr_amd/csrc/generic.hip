@@ -9,7 +9,7 @@
 // matrices Ke_e (MG.hh:604-669).  The same gather yields S = sum_e (K_e u_e)[node rows] and the diagonal block M, so
 // the operator apply, the residual and the multicoloured block Gauss-Seidel (MG.hh:193-340) share it.  Deterministic:
 // fixed lane ownership and a fixed xor-shuffle reduction tree.
-#include "vfem_internal.h"
+#include "vfem_host.h"
 #include "q2_modes.h"
 
 
@@ -639,14 +639,13 @@ struct vfem_gsim {
     double E0 = 1.0, Emin = 1e-9, gamma = 3.0;     // TPS.hh:1392-1394
     std::vector<double> K0;
     DevBuf<double> dK0, rho, E, dvals;
-    DevBuf<double> red;                            // scratch of the compliance reduction
     DevBuf<double> q2tab;                          // degree-2 hexahedra: packed mode-space blocks (q2_modes.h)
     DevBuf<double> q2gstab;                        // ... and K0 regrouped for the finest-level sweep ordered by neighbour node
-    int transfer_axis = 1;                         // vfem_gsim_set_option(17, v): 3-D grid transfers axis by axis (1) or in one pass (0)
-    int q2_gs_impl = 2;                            // vfem_gsim_set_option(16, v): finest-level sweep 0 by element, 1 by neighbour node, 2 the same with the neighbour rows staged through LDS
+    int transfer_axis = 1;                         // VFEM_OPT_TRANSFER_AXIS: 3-D grid transfers axis by axis (1) or in one pass (0)
+    int q2_gs_impl = 2;                            // VFEM_OPT_Q2_GS_IMPL: finest-level sweep 0 by element, 1 by neighbour node, 2 the same with the neighbour rows staged through LDS
     bool q2_fast = false;
-    int q2_l1_virtual = 2;                         // vfem_gsim_set_option(14, v): level 1 of a degree-2 hierarchy 0 stored, 1 virtual, 2 by size
-    int q2_impl = 0;                               // vfem_gsim_set_option(6, v): 0 marching kernel (mode space), 1 dense gather kernel (cross-check), 2 pencil kernel
+    int q2_l1_virtual = 2;                         // VFEM_OPT_Q2_L1_VIRTUAL: level 1 of a degree-2 hierarchy 0 stored, 1 virtual, 2 by size
+    int q2_impl = 0;                               // VFEM_OPT_Q2_IMPL: 0 marching kernel (mode space), 1 dense gather kernel (cross-check), 2 pencil kernel
     DevBuf<uint8_t> dmask;
     std::vector<uint8_t> hmask;
     bool nonzero_dirichlet = false;
@@ -795,10 +794,6 @@ void vfem_gsim::update_k0() {
         }
     }
 }
-
-static inline hipStream_t GS(void *s) { return (hipStream_t) s; }
-#define G_TRY try {
-#define G_CATCH } catch (const std::exception &e) { vfem::set_error(e.what()); return 1; } return 0;
 
 static void g_apply(const GDims &d, const double *K, long long kstride, const double *scale, const double *u,
                     const double *b, const uint8_t *mask, int mode, double *out, hipStream_t s) {
@@ -1089,40 +1084,11 @@ static void gmg_cycles(vfem_gmg *mg, int num_steps, int nsmooth, bool zero_diric
         for (int i = 0; i < num_steps; ++i) gmg_vcycle(mg, 0, nsmooth, zero_dirichlet, s);
 }
 
-static void coarsen_mask(const GDims &f, const std::vector<uint8_t> &fm, const GDims &c, std::vector<uint8_t> &cm) {
-    // MG.hh:57-84 in integer arithmetic
-    const int N = f.N, p = f.p;
-    cm.assign((size_t) c.nnodes, 0);
-    for (long long nf = 0; nf < f.nnodes; ++nf) {
-        const uint8_t m = fm[nf];
-        if (!m) continue;
-        int g[3] = {0, 0, 0};
-        { long long q = nf; for (int a = N - 1; a >= 0; --a) { g[a] = (int) (q % f.nn[a]); q /= f.nn[a]; } }
-        int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-        bool any = false;
-        for (int a = 0; a < N; ++a) {
-            const int e = std::min(g[a] / (2 * p), c.ne[a] - 1), t = g[a] - 2 * p * e;
-            if (t == 0) { lo[a] = hi[a] = p * e; any = true; }
-            else if (t == 2 * p) { lo[a] = hi[a] = p * e + p; any = true; }
-            else { lo[a] = p * e; hi[a] = p * e + p; }
-        }
-        if (!any) throw Error("Dirichlet constraints on internal nodes are not supported");
-        for (int a0 = lo[0]; a0 <= hi[0]; ++a0)
-            for (int a1 = lo[1]; a1 <= hi[1]; ++a1)
-                for (int a2 = lo[2]; a2 <= hi[2]; ++a2) {
-                    const int gg[3] = {a0, a1, a2};
-                    long long node = gg[0];
-                    for (int a = 1; a < N; ++a) node = node * c.nn[a] + gg[a];
-                    cm[node] |= m;
-                }
-    }
-}
-
 extern "C" {
 
 int vfem_gsim_create_padded(vfem_gsim **out, int dim, int degree, const double *bbmin, const double *bbmax, const int64_t *ne,
                             int64_t ex_lo, int64_t ex_hi) {
-    G_TRY
+    VFEM_TRY
     if (dim != 2 && dim != 3) throw Error("dimension must be 2 or 3");
     if (degree != 1 && degree != 2) throw Error("No template instantiation matching degreesPerDimension!");
     long long n[3] = {1, 1, 1};
@@ -1147,39 +1113,39 @@ int vfem_gsim_create_padded(vfem_gsim **out, int dim, int degree, const double *
     sim->dvals.alloc((size_t) sim->d.nnodes * dim); sim->dvals.zero(nullptr);
     VFEM_HIP(hipDeviceSynchronize());
     *out = sim.release();
-    G_CATCH
+    VFEM_CATCH
 }
 int vfem_gsim_create(vfem_gsim **out, int dim, int degree, const double *bbmin, const double *bbmax, const int64_t *ne) {
     return vfem_gsim_create_padded(out, dim, degree, bbmin, bbmax, ne, 0, 0);
 }
-int vfem_gsim_destroy(vfem_gsim *sim) { G_TRY delete sim; G_CATCH }
+int vfem_gsim_destroy(vfem_gsim *sim) { VFEM_TRY delete sim; VFEM_CATCH }
 int64_t vfem_gsim_num_stored_elements(const vfem_gsim *sim) { return sim->stored_elems(); }
 int64_t vfem_gsim_num_nodes(const vfem_gsim *sim) { return sim->d.nnodes; }
 int64_t vfem_gsim_num_elements(const vfem_gsim *sim) { return sim->d.nelems; }
 int vfem_gsim_ke_size(const vfem_gsim *sim) { return sim->d.ke; }
 int vfem_gsim_set_isotropic(vfem_gsim *sim, double young, double poisson) {
-    G_TRY
+    VFEM_TRY
     // ElasticityTensor::setIsotropic (ElasticityTensor.hh:100-133): 3-D Lame parameters; 2-D = plane stress
     sim->lambda = sim->d.N == 2 ? poisson * young / (1.0 - poisson * poisson)
                                 : poisson * young / ((1.0 + poisson) * (1.0 - 2.0 * poisson));
     sim->mu = young / (2.0 + 2.0 * poisson);
     sim->update_k0();
     ++sim->operator_version;
-    G_CATCH
+    VFEM_CATCH
 }
 int vfem_gsim_set_simp(vfem_gsim *sim, double E0, double Emin, double gamma) {
-    G_TRY
+    VFEM_TRY
     sim->E0 = E0; sim->Emin = Emin; sim->gamma = gamma;
     ++sim->operator_version;
     sim->update_E(nullptr);
     VFEM_HIP(hipDeviceSynchronize());
-    G_CATCH
+    VFEM_CATCH
 }
 int vfem_gsim_k0(const vfem_gsim *sim, double *K0_host) {
-    G_TRY std::memcpy(K0_host, sim->K0.data(), sim->K0.size() * sizeof(double)); G_CATCH
+    VFEM_TRY std::memcpy(K0_host, sim->K0.data(), sim->K0.size() * sizeof(double)); VFEM_CATCH
 }
 int vfem_gsim_set_dirichlet(vfem_gsim *sim, const uint8_t *mask_host, const double *values_host) {
-    G_TRY
+    VFEM_TRY
     sim->hmask.assign(mask_host, mask_host + sim->d.nnodes);
     sim->nonzero_dirichlet = false;
     for (long long n = 0; n < sim->d.nnodes; ++n)
@@ -1188,48 +1154,48 @@ int vfem_gsim_set_dirichlet(vfem_gsim *sim, const uint8_t *mask_host, const doub
     ++sim->operator_version;
     VFEM_HIP(hipMemcpy(sim->dmask.p, mask_host, (size_t) sim->d.nnodes, hipMemcpyHostToDevice));
     VFEM_HIP(hipMemcpy(sim->dvals.p, values_host, (size_t) sim->d.nnodes * sim->d.N * sizeof(double), hipMemcpyHostToDevice));
-    G_CATCH
+    VFEM_CATCH
 }
 int vfem_gsim_set_densities(vfem_gsim *sim, const double *rho, void *stream) {
-    G_TRY
+    VFEM_TRY
     // padded simulators take all stored layers (ex_lo + ne[0] + ex_hi), x slowest
-    VFEM_HIP(hipMemcpyAsync(sim->rho.p, rho, (size_t) sim->stored_elems() * sizeof(double), hipMemcpyDeviceToDevice, GS(stream)));
+    VFEM_HIP(hipMemcpyAsync(sim->rho.p, rho, (size_t) sim->stored_elems() * sizeof(double), hipMemcpyDeviceToDevice, S(stream)));
     ++sim->operator_version;
-    sim->update_E(GS(stream));
-    G_CATCH
+    sim->update_E(S(stream));
+    VFEM_CATCH
 }
 int vfem_gsim_get_densities(const vfem_gsim *sim, double *rho, void *stream) {
-    G_TRY
-    VFEM_HIP(hipMemcpyAsync(rho, sim->rho_local(), (size_t) sim->d.nelems * sizeof(double), hipMemcpyDeviceToDevice, GS(stream)));
-    G_CATCH
+    VFEM_TRY
+    VFEM_HIP(hipMemcpyAsync(rho, sim->rho_local(), (size_t) sim->d.nelems * sizeof(double), hipMemcpyDeviceToDevice, S(stream)));
+    VFEM_CATCH
 }
 int vfem_gsim_set_option(vfem_gsim *sim, int key, int value) {
-    G_TRY
-    if (key == 6 && value >= 0 && value <= 2) sim->q2_impl = value;
-    else if (key == 14 && value >= 0 && value <= 2) sim->q2_l1_virtual = value;
-    else if (key == 16 && value >= 0 && value <= 2) sim->q2_gs_impl = value;
-    else if (key == 17 && (value == 0 || value == 1)) sim->transfer_axis = value;
+    VFEM_TRY
+    if (key == VFEM_OPT_Q2_IMPL && value >= 0 && value <= 2) sim->q2_impl = value;
+    else if (key == VFEM_OPT_Q2_L1_VIRTUAL && value >= 0 && value <= 2) sim->q2_l1_virtual = value;
+    else if (key == VFEM_OPT_Q2_GS_IMPL && value >= 0 && value <= 2) sim->q2_gs_impl = value;
+    else if (key == VFEM_OPT_TRANSFER_AXIS && (value == 0 || value == 1)) sim->transfer_axis = value;
     else throw Error("unknown option or value out of range");
-    G_CATCH
+    VFEM_CATCH
 }
 int vfem_gsim_apply_k(const vfem_gsim *sim, const double *u, double *out, void *stream) {
-    G_TRY
+    VFEM_TRY
     if (sim->d.N == 3 && sim->d.p == 2 && sim->q2_fast && sim->q2_impl == 0)
-        launch_apply_q2_march(sim->d.ne[0], sim->d.ne[1], sim->d.ne[2], sim->q2tab.p, sim->E_local(), u, out, GS(stream));
+        launch_apply_q2_march(sim->d.ne[0], sim->d.ne[1], sim->d.ne[2], sim->q2tab.p, sim->E_local(), u, out, S(stream));
     else if (sim->d.N == 3 && sim->d.p == 2 && sim->q2_fast && sim->q2_impl == 2)
-        launch_apply_q2_pencil(sim->d.ne[0], sim->d.ne[1], sim->d.ne[2], sim->q2tab.p, sim->E_local(), u, out, GS(stream));
+        launch_apply_q2_pencil(sim->d.ne[0], sim->d.ne[1], sim->d.ne[2], sim->q2tab.p, sim->E_local(), u, out, S(stream));
     else if (sim->d.N == 3 && sim->d.p == 2)
-        launch_apply_q2(sim->d.ne[0], sim->d.ne[1], sim->d.ne[2], sim->dK0.p, sim->E_local(), u, out, GS(stream));
+        launch_apply_q2(sim->d.ne[0], sim->d.ne[1], sim->d.ne[2], sim->dK0.p, sim->E_local(), u, out, S(stream));
     else
-        g_apply(sim->d, sim->dK0.p, 0, sim->E_local(), u, nullptr, nullptr, 0, out, GS(stream));
-    G_CATCH
+        g_apply(sim->d, sim->dK0.p, 0, sim->E_local(), u, nullptr, nullptr, 0, out, S(stream));
+    VFEM_CATCH
 }
 int vfem_gsim_direct_solve(vfem_gsim *sim, const double *f, double *u, void *stream) {
-    G_TRY
+    VFEM_TRY
     if (sim->nonzero_dirichlet) throw Error("Nonzero Dirichlet constraints currently unsupported");
     band_direct_solve(sim->direct, sim->operator_version, sim->d.N, sim->d.p, sim->d.ne, sim->dK0.p, sim->E_local(), sim->dmask.p, f, u,
-                      GS(stream));
-    G_CATCH
+                      S(stream));
+    VFEM_CATCH
 }
 int64_t vfem_gsim_direct_factorizations(const vfem_gsim *sim) { return sim->direct.factorizations; }
 int64_t vfem_gsim_direct_band_bytes(const vfem_gsim *sim) {
@@ -1238,25 +1204,17 @@ int64_t vfem_gsim_direct_band_bytes(const vfem_gsim *sim) {
     return band_spd_doubles(n, w) * (int64_t) sizeof(double);
 }
 int vfem_gsim_compliance_gradient(const vfem_gsim *sim, const double *u, double *g, void *stream) {
-    G_TRY
-    kg_gradient<<<dim3((unsigned) ((sim->d.nelems + 3) / 4)), dim3(256), 0, GS(stream)>>>(sim->d, sim->dK0.p, sim->rho_local(), sim->E0, sim->Emin,
+    VFEM_TRY
+    kg_gradient<<<dim3((unsigned) ((sim->d.nelems + 3) / 4)), dim3(256), 0, S(stream)>>>(sim->d, sim->dK0.p, sim->rho_local(), sim->E0, sim->Emin,
                                                                                        sim->gamma, u, g);
     VFEM_HIP(hipGetLastError());
-    G_CATCH
+    VFEM_CATCH
 }
 
 int vfem_gsim_compliance(const vfem_gsim *sim, const double *f, const double *u, double *value_host, void *stream) {
-    G_TRY
-    // stream-ordered scratch (hipMallocAsync does not synchronise the device): evaluations on different streams share nothing
-    double *tmp = nullptr;
-    VFEM_HIP(hipMallocAsync((void **) &tmp, (4096 + 1) * sizeof(double), GS(stream)));
-    launch_dot((long long) sim->d.N * sim->d.nnodes, f, u, tmp, tmp + 4096, GS(stream));
-    double v = 0.0;
-    VFEM_HIP(hipMemcpyAsync(&v, tmp + 4096, sizeof(double), hipMemcpyDeviceToHost, GS(stream)));
-    VFEM_HIP(hipFreeAsync(tmp, GS(stream)));
-    VFEM_HIP(hipStreamSynchronize(GS(stream)));
-    *value_host = 0.5 * v;                                            // TopologyOptimizationObjective.hh:39-41
-    G_CATCH
+    VFEM_TRY
+    *value_host = compliance((long long) sim->d.N * sim->d.nnodes, f, u, S(stream));
+    VFEM_CATCH
 }
 
 // interpolation weights, compressed interpolation operators phi[fi](fine_n, coarse_n) (MG.hh:557-583) and
@@ -1280,22 +1238,7 @@ static void gmg_setup_transfer_tables(vfem_gmg *mg) {
                 }
                 ph[fn * npe + cn] = w;
             }
-        const std::vector<double> &K0 = fine->K0;
-        for (int i = 0; i < ke; ++i)
-            for (int j = 0; j < ke; ++j) {
-                const int m = j / N, b = j % N;
-                double v = 0.0;
-                for (int qn = 0; qn < npe; ++qn) v += K0[(size_t) i * ke + N * qn + b] * ph[qn * npe + m];
-                T[(size_t) i * ke + j] = v;
-            }
-        double *cK = cK0.data() + (size_t) fi * ke * ke;
-        for (int i = 0; i < ke; ++i)
-            for (int j = 0; j < ke; ++j) {
-                const int n = i / N, a = i % N;
-                double v = 0.0;
-                for (int pn = 0; pn < npe; ++pn) v += ph[pn * npe + n] * T[(size_t) (N * pn + a) * ke + j];
-                cK[(size_t) i * ke + j] = v;
-            }
+        galerkin_project(fine->K0.data(), ke, N, npe, ph, T.data(), cK0.data() + (size_t) fi * ke * ke);
     }
     if (N == 3 && p == 2) {
         std::vector<double> tab((size_t) 27 * 27 * 72);
@@ -1310,27 +1253,12 @@ static void gmg_setup_transfer_tables(vfem_gmg *mg) {
     }
     if (N == 3 && p == 2) {
         // c2K0[g][f] = I_g^T cK0[f] I_g, stored [entry][8 g + f] for kg_coarsen_level2_q2
-        std::vector<double> t2((size_t) 6561 * 64), T2((size_t) ke * ke);
-        for (int g = 0; g < 8; ++g) {
-            const double *ph = phi.data() + (size_t) g * npe * npe;
+        std::vector<double> t2((size_t) 6561 * 64), c2((size_t) ke * ke);
+        for (int g = 0; g < 8; ++g)
             for (int f = 0; f < 8; ++f) {
-                const double *A = cK0.data() + (size_t) f * ke * ke;
-                for (int i = 0; i < ke; ++i)
-                    for (int j = 0; j < ke; ++j) {
-                        const int m = j / N, b = j % N;
-                        double v = 0.0;
-                        for (int qn = 0; qn < npe; ++qn) v += A[(size_t) i * ke + N * qn + b] * ph[qn * npe + m];
-                        T2[(size_t) i * ke + j] = v;
-                    }
-                for (int i = 0; i < ke; ++i)
-                    for (int j = 0; j < ke; ++j) {
-                        const int n = i / N, a = i % N;
-                        double v = 0.0;
-                        for (int pn = 0; pn < npe; ++pn) v += ph[pn * npe + n] * T2[(size_t) (N * pn + a) * ke + j];
-                        t2[((size_t) i * ke + j) * 64 + 8 * g + f] = v;
-                    }
+                galerkin_project(cK0.data() + (size_t) f * ke * ke, ke, N, npe, phi.data() + (size_t) g * npe * npe, T.data(), c2.data());
+                for (size_t q = 0; q < c2.size(); ++q) t2[q * 64 + 8 * g + f] = c2[q];
             }
-        }
         mg->c2tab.alloc(t2.size());
         VFEM_HIP(hipMemcpy(mg->c2tab.p, t2.data(), t2.size() * sizeof(double), hipMemcpyHostToDevice));
     }
@@ -1350,7 +1278,7 @@ static void gmg_alloc_level_fields(GLevel &lv) {
 // the element matrices of level first_active are imported (vfem_gmg_import_level_ke), cycles start there
 // (vfem_gmg_cycle_from_level); `fine` supplies the grid, the material and the Dirichlet mask only.
 static int gmg_create_common(vfem_gmg **out, vfem_gsim *fine, int L, int first_active) {
-    G_TRY
+    VFEM_TRY
     if (L < 0 || L > 16) throw Error("invalid number of coarsening levels");
     if (first_active < 0 || first_active > L) throw Error("first active level out of range");
     if (fine->ex_lo || fine->ex_hi) throw Error("simulators with element padding need vfem_gmg_create_slab");
@@ -1368,7 +1296,7 @@ static int gmg_create_common(vfem_gmg **out, vfem_gsim *fine, int L, int first_a
             }
         }
         lv.d = make_gdims(N, p, ne);
-        if (l == 0) lv.hmask = fine->hmask; else coarsen_mask(mg->lv[l - 1].d, mg->lv[l - 1].hmask, lv.d, lv.hmask);
+        if (l == 0) lv.hmask = fine->hmask; else coarsen_dirichlet_mask(N, p, mg->lv[l - 1].d.nn, mg->lv[l - 1].hmask, lv.d.ne, lv.hmask);
         if (l >= first_active) gmg_alloc_level_fields(lv);
     }
     gmg_setup_transfer_tables(mg.get());
@@ -1376,10 +1304,10 @@ static int gmg_create_common(vfem_gmg **out, vfem_gsim *fine, int L, int first_a
         const size_t n0 = (size_t) fine->d.nnodes * N;
         mg->pr.alloc(n0); mg->pd.alloc(n0); mg->pAd.alloc(n0); mg->ps.alloc(n0);
     }
-    mg->scal.alloc(8); mg->scal.zero(nullptr); mg->scratch.alloc(4096);
+    mg->scal.alloc(8); mg->scal.zero(nullptr); mg->scratch.alloc(REDUCE_SCRATCH_DOUBLES);
     VFEM_HIP(hipDeviceSynchronize());
     *out = mg.release();
-    G_CATCH
+    VFEM_CATCH
 }
 int vfem_gmg_create(vfem_gmg **out, vfem_gsim *fine, int L) { return gmg_create_common(out, fine, L, 0); }
 int vfem_gmg_create_partial(vfem_gmg **out, vfem_gsim *fine, int L, int first_active_level) {
@@ -1393,7 +1321,7 @@ int vfem_gmg_create_partial(vfem_gmg **out, vfem_gsim *fine, int L, int first_ac
 // driver aligns the slabs so that every local grid starts at an even global element (the colours need no offset then).
 // masks_host[l]: the level's Dirichlet masks (slices of the global coarsened masks).  The last level only serves the transfers.
 int vfem_gmg_create_slab(vfem_gmg **out, vfem_gsim *fine, int n_levels, const vfem_slab_level *lv_in, const uint8_t *const *masks_host) {
-    G_TRY
+    VFEM_TRY
     if (n_levels < 1) throw Error("need at least one level");
     if (fine->d.N != 3) throw Error("slab hierarchies are three-dimensional");
     std::unique_ptr<vfem_gmg> mg(new vfem_gmg);
@@ -1418,62 +1346,62 @@ int vfem_gmg_create_slab(vfem_gmg **out, vfem_gsim *fine, int n_levels, const vf
     if (fine->d.ne[0] != mg->lv[0].d.ne[0] || fine->ex_lo != mg->lv[0].pad_lo || fine->ex_hi != mg->lv[0].pad_hi)
         throw Error("level 0 of the slab hierarchy does not match the simulator");
     gmg_setup_transfer_tables(mg.get());
-    mg->scal.alloc(8); mg->scal.zero(nullptr); mg->scratch.alloc(4096);
+    mg->scal.alloc(8); mg->scal.zero(nullptr); mg->scratch.alloc(REDUCE_SCRATCH_DOUBLES);
     VFEM_HIP(hipDeviceSynchronize());
     *out = mg.release();
-    G_CATCH
+    VFEM_CATCH
 }
 int vfem_gmg_destroy(vfem_gmg *mg) {
-    G_TRY
+    VFEM_TRY
     delete mg;
-    G_CATCH
+    VFEM_CATCH
 }
 int vfem_gmg_num_levels(const vfem_gmg *mg) { return mg->L + 1; }
 int vfem_gmg_level_dims(const vfem_gmg *mg, int level, int64_t ne[3]) {
-    G_TRY
+    VFEM_TRY
     if (level < 0 || level > mg->L) throw Error("level out of range");
     for (int a = 0; a < 3; ++a) ne[a] = mg->lv[level].d.ne[a];
-    G_CATCH
+    VFEM_CATCH
 }
 int64_t vfem_gmg_level_num_nodes(const vfem_gmg *mg, int level) { return (level < 0 || level > mg->L) ? -1 : mg->lv[level].d.nnodes; }
 int vfem_gmg_level_dirichlet_mask(const vfem_gmg *mg, int level, uint8_t *mask_host) {
-    G_TRY
+    VFEM_TRY
     if (level < 0 || level > mg->L) throw Error("level out of range");
     std::memcpy(mask_host, mg->lv[level].hmask.data(), mg->lv[level].hmask.size());
-    G_CATCH
+    VFEM_CATCH
 }
 int vfem_gmg_set_symmetric_gauss_seidel(vfem_gmg *mg, int symmetric) { mg->symmetric_gs = symmetric != 0; return 0; }
-int vfem_gmg_update_operators(vfem_gmg *mg, void *stream) { G_TRY gmg_update(mg, GS(stream)); G_CATCH }
+int vfem_gmg_update_operators(vfem_gmg *mg, void *stream) { VFEM_TRY gmg_update(mg, S(stream)); VFEM_CATCH }
 static void g_check_level(const vfem_gmg *mg, int level, bool need_ops) {
     if (level < 0 || level > mg->L) throw Error("level out of range");
     if (need_ops && (level > 0 || mg->external_ke_level == 0) && !mg->operators_valid) throw Error("coarse operators not built: call updateElementStiffnessMatrices first");
 }
 int vfem_gmg_apply_k(vfem_gmg *mg, int level, const double *u, double *out, void *stream) {
-    G_TRY g_check_level(mg, level, true); gmg_apply(mg, level, u, nullptr, 0, out, GS(stream)); G_CATCH
+    VFEM_TRY g_check_level(mg, level, true); gmg_apply(mg, level, u, nullptr, 0, out, S(stream)); VFEM_CATCH
 }
 int vfem_gmg_residual(vfem_gmg *mg, int level, const double *u, const double *b, double *r, void *stream) {
-    G_TRY g_check_level(mg, level, true); gmg_apply(mg, level, u, b, 1, r, GS(stream)); G_CATCH
+    VFEM_TRY g_check_level(mg, level, true); gmg_apply(mg, level, u, b, 1, r, S(stream)); VFEM_CATCH
 }
 int vfem_gmg_smooth(vfem_gmg *mg, int level, double *u, const double *b, int forward, void *stream) {
-    G_TRY g_check_level(mg, level, true); gmg_smooth(mg, level, u, b, forward, GS(stream)); G_CATCH
+    VFEM_TRY g_check_level(mg, level, true); gmg_smooth(mg, level, u, b, forward, S(stream)); VFEM_CATCH
 }
 int vfem_gmg_smooth_colors(vfem_gmg *mg, int level, double *u, const double *b, int forward, int first, int count, void *stream) {
-    G_TRY
+    VFEM_TRY
     g_check_level(mg, level, true);
     int ncol = 1;
     for (int a = 0; a < mg->fine->d.N; ++a) ncol *= mg->fine->d.p + 1;
     if (first < 0 || count < 0 || first + count > ncol) throw Error("colour range out of bounds");
-    gmg_smooth(mg, level, u, b, forward, GS(stream), first, count);
-    G_CATCH
+    gmg_smooth(mg, level, u, b, forward, S(stream), first, count);
+    VFEM_CATCH
 }
 // one cycle of the replicated coarse hierarchy on the residual system of `level` (x = 0 initial guess for the full cycle)
 int vfem_gmg_cycle_from_level(vfem_gmg *mg, int level, double *x, const double *b, int nsmooth, int fmg, void *stream) {
-    G_TRY
+    VFEM_TRY
     g_check_level(mg, level, false);
     if (level < mg->first_active) throw Error("level below the first active level of this hierarchy");
     if (mg->slab) throw Error("slab hierarchies are cycled by the distributed driver");
     if (!mg->operators_valid) throw Error("coarse operators not built: call vfem_gmg_update_operators first");
-    hipStream_t s = GS(stream);
+    hipStream_t s = S(stream);
     GLevel &L = mg->lv[level];
     const size_t bytes = (size_t) L.d.nnodes * L.d.N * sizeof(double);
     VFEM_HIP(hipMemcpyAsync(L.b.p, b, bytes, hipMemcpyDeviceToDevice, s));
@@ -1483,12 +1411,12 @@ int vfem_gmg_cycle_from_level(vfem_gmg *mg, int level, double *x, const double *
         gmg_vcycle(mg, level, nsmooth, true, s);
     }
     VFEM_HIP(hipMemcpyAsync(x, L.x.p, bytes, hipMemcpyDeviceToDevice, s));
-    G_CATCH
+    VFEM_CATCH
 }
 // Galerkin element matrices of `count_x` element layers of `level` computed from their children, which start at stored layer
 // `child_first_layer` of level - 1 (level 1: of the simulator's moduli): what a rank contributes to the first replicated level
 int vfem_gmg_export_level_ke(vfem_gmg *mg, int level, int64_t child_first_layer, int64_t count_x, double *ke_out, void *stream) {
-    G_TRY
+    VFEM_TRY
     g_check_level(mg, level, false);
     if (level < 1) throw Error("level 0 has no stored element matrices");
     if (level > 1 && !mg->operators_valid) throw Error("coarse operators not built: call vfem_gmg_update_operators first");
@@ -1499,40 +1427,40 @@ int vfem_gmg_export_level_ke(vfem_gmg *mg, int level, int64_t child_first_layer,
     const GDims c = make_gdims(3, lv.d.p, cne), f = make_gdims(3, lv.d.p, fne);
     if (level == 2 && mg->l1_virtual) {
         if (child_first_layer % 2) throw Error("child layers must start at an even stored layer");
-        coarsen_through_virtual_level1(mg, child_first_layer / 2, count_x, ke_out, GS(stream));
+        coarsen_through_virtual_level1(mg, child_first_layer / 2, count_x, ke_out, S(stream));
         return 0;
     }
     const size_t child_stride = level == 1 ? 1 : (size_t) lv.d.ke * lv.d.ke;
     const double *src = (level == 1 ? mg->fine->E.p : mg->lv[level - 1].Ke.p) + (size_t) child_first_layer * fs.ne[1] * fs.ne[2] * child_stride;
-    g_coarsen(mg, f, c, level == 1, src, ke_out, GS(stream));
-    G_CATCH
+    g_coarsen(mg, f, c, level == 1, src, ke_out, S(stream));
+    VFEM_CATCH
 }
 int vfem_gmg_import_level_ke(vfem_gmg *mg, int level, const double *ke, void *stream) {
-    G_TRY
+    VFEM_TRY
     g_check_level(mg, level, false);
     if (mg->slab) throw Error("element matrices are imported into replicated hierarchies only");
     if (level != mg->first_active) throw Error("element matrices are imported into the first active level (level 0 of a hierarchy created on the coarse grid itself)");
     GLevel &lv = mg->lv[level];
     const size_t n = (size_t) lv.d.nelems * lv.d.ke * lv.d.ke;
     lv.Ke.alloc(n);
-    VFEM_HIP(hipMemcpyAsync(lv.Ke.p, ke, n * sizeof(double), hipMemcpyDeviceToDevice, GS(stream)));
+    VFEM_HIP(hipMemcpyAsync(lv.Ke.p, ke, n * sizeof(double), hipMemcpyDeviceToDevice, S(stream)));
     mg->external_ke_level = level;
     mg->operators_valid = false;
-    G_CATCH
+    VFEM_CATCH
 }
 int vfem_gmg_zero_dirichlet(vfem_gmg *mg, int level, double *u, void *stream) {
-    G_TRY g_check_level(mg, level, false); g_dirichlet(mg->lv[level].d, mg->lv[level].mask.p, nullptr, u, GS(stream)); G_CATCH
+    VFEM_TRY g_check_level(mg, level, false); g_dirichlet(mg->lv[level].d, mg->lv[level].mask.p, nullptr, u, S(stream)); VFEM_CATCH
 }
 int vfem_gmg_restrict(vfem_gmg *mg, int fine_level, const double *fine, double *coarse, void *stream) {
-    G_TRY g_check_level(mg, fine_level + 1, false); gmg_restrict(mg, fine_level, fine, coarse, GS(stream)); G_CATCH
+    VFEM_TRY g_check_level(mg, fine_level + 1, false); gmg_restrict(mg, fine_level, fine, coarse, S(stream)); VFEM_CATCH
 }
 int vfem_gmg_interpolate(vfem_gmg *mg, int fine_level, const double *coarse, double *fine, int accumulate, void *stream) {
-    G_TRY g_check_level(mg, fine_level + 1, false); gmg_prolong(mg, fine_level, coarse, fine, accumulate, GS(stream)); G_CATCH
+    VFEM_TRY g_check_level(mg, fine_level + 1, false); gmg_prolong(mg, fine_level, coarse, fine, accumulate, S(stream)); VFEM_CATCH
 }
 int vfem_gmg_solve(vfem_gmg *mg, double *x, const double *f, int num_steps, int nsmooth, int stiffness_updated,
                    int zero_dirichlet, int fmg, void *stream) {
-    G_TRY
-    hipStream_t s = GS(stream);
+    VFEM_TRY
+    hipStream_t s = S(stream);
     if (mg->slab || mg->first_active > 0) throw Error("slab / partial hierarchies are cycled by the distributed driver");
     if (!stiffness_updated) gmg_update(mg, s);                         // MG.hh:455
     else if (!mg->operators_valid) throw Error("coarse operators not built");
@@ -1542,12 +1470,12 @@ int vfem_gmg_solve(vfem_gmg *mg, double *x, const double *f, int num_steps, int 
     VFEM_HIP(hipMemcpyAsync(mg->lv[0].b.p, f, bytes, hipMemcpyDeviceToDevice, s));
     gmg_cycles(mg, num_steps, nsmooth, zero_dirichlet != 0, fmg != 0, s);
     VFEM_HIP(hipMemcpyAsync(x, mg->lv[0].x.p, bytes, hipMemcpyDeviceToDevice, s));
-    G_CATCH
+    VFEM_CATCH
 }
 int vfem_gmg_pcg(vfem_gmg *mg, double *x, const double *b, int max_iter, double tol, int mg_iterations, int mg_smoothing,
                  int fmg, vfem_residual_cb residual_cb, void *cb_user, int *iters_out, double *relres_out, void *stream) {
-    G_TRY
-    hipStream_t s = GS(stream);
+    VFEM_TRY
+    hipStream_t s = S(stream);
     if (mg->slab || mg->first_active > 0) throw Error("slab / partial hierarchies are solved by the distributed driver");
     vfem_gsim *sim = mg->fine;
     const long long nn = sim->d.nnodes, n3 = sim->d.N * nn;
@@ -1591,7 +1519,7 @@ int vfem_gmg_pcg(vfem_gmg *mg, double *x, const double *b, int max_iter, double 
     }
     if (iters_out) *iters_out = it;
     if (relres_out) *relres_out = bb > 0 ? std::sqrt(rr / bb) : 0.0;
-    G_CATCH
+    VFEM_CATCH
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// argument block of the fused MLP kernel (shared by capi.hip and kernels_mlp.hip)
+// argument block of the fused MLP kernel (shared by mlp.hip and the kernels_mlp*.hip)
 #pragma once
 namespace vfem {
 struct MlpArgs {

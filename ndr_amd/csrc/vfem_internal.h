@@ -268,7 +268,7 @@ void launch_adam(long long n, float *p, const float *g, float *m, float *v, floa
 // ------------------------------------------------------------------------------------------
 struct vfem_sim {
     vfem::Dims d;
-    double bbmin[3], bbmax[3], h[3];
+    double h[3];
     double lambda = 0.0, mu = 0.5;              // ETensor(1, 0) default, TPS.hh:1379
     double E0 = 1.0, Emin = 1e-9, gamma = 3.0;  // TPS.hh:1392-1394
     double K0[576];                             // host copy, row-major
@@ -285,7 +285,6 @@ struct vfem_sim {
     long long ex_lo = 0, ex_hi = 0;
     long long operator_version = 1;             // bumped whenever K(rho) changes (densities, SIMP law, material): hierarchies rebuild
     vfem::Tuning tune;
-    vfem::DevBuf<double> red;                   // scratch of the reductions (vfem_compliance)
     vfem::BandSolver direct;                    // factorisation of TPS::solve (vfem_sim_direct_solve)
     long long n_store() const { return (long long) (d.nx + ex_lo + ex_hi) * d.ny * d.nz; }
     const double *Ep() const { return E.p + ex_lo * d.ny * d.nz; }
@@ -299,7 +298,6 @@ struct MgLevel {
     long long ex_lo = 0, ex_hi = 0;
     int xshift = 0;                             // finer-level local plane of this level's local plane 0
     int xparity = 0;                            // global x-parity of local plane 0
-    int fineNX = 0;                             // node planes of the next finer level (for the transfers)
     vfem::OpKind kind = vfem::OP_MF0;
     vfem::DevBuf<uint8_t> mask;                 // coarsened Dirichlet masks (levels >= 1)
     const uint8_t *maskp = nullptr;
@@ -323,7 +321,7 @@ struct vfem_mg {
     vfem::DevBuf<double> l1mtab;                // cK0[0] by mirror class (build_l1_merged_table)
     vfem::DevBuf<double> c2K0;                  // 64 x 576: I_g^T cK0[f] I_g (level-2 element matrices from the fine moduli)
     vfem::DevBuf<double> Ainv;                  // coarsest-level dense inverse
-    vfem::DevBuf<double> pr, pd, pAd, ps;       // PCG vectors
+    vfem::DevBuf<double> pd, pAd, ps;           // PCG vectors (the residual lives in lv[0].b)
     vfem::DevBuf<double> scal, scratch;
     bool slab = false;                          // local part of an x-slab decomposition: no coarsest solver here
     int first_active = 0;                       // levels below are never cycled (replicated coarse hierarchy)

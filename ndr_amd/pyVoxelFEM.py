@@ -825,9 +825,7 @@ class TensorProductSimulator1_1_1(_Simulator):
     _GETK_MAX_ELEMENTS = 1 << 21
 
     def _create(self, out, lo, hi, ne, pad_lo, pad_hi):
-        # the padding of a slab simulator is a one-shot setting that the next vfem_sim_create consumes
-        _lib.check(self._c("set_next_element_padding")(pad_lo, pad_hi))
-        return self._c("create")(out, lo, hi, ne)
+        return self._c("create_padded")(out, lo, hi, ne, pad_lo, pad_hi)
 
     @property
     def ETensor(self):

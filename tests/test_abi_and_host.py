@@ -45,6 +45,49 @@ def test_no_gpu_means_loud_failure():
         pv.TensorProductSimulator([1, 1, 1], [np.zeros(3), np.ones(3)], [4, 4, 4])
 
 
+def _create_padded(lib, ne, pad):
+    import ctypes
+    h = ctypes.c_void_p()
+    lo, hi, n = (ctypes.c_double * 3)(0, 0, 0), (ctypes.c_double * 3)(1, 1, 1), (ctypes.c_int64 * 3)(*ne)
+    return lib.vfem_sim_create_padded(ctypes.byref(h), lo, hi, n, pad[0], pad[1]), h
+
+
+def test_padded_create_refuses_negative_padding():
+    """the argument checks of vfem_sim_create_padded come before any device call: error code 1, a message, no handle"""
+    from ndr_amd import _lib
+    lib = _lib.load()
+    assert not hasattr(lib, "vfem_sim_set_next_element_padding")
+    for pad in ((-1, 0), (0, -1)):
+        rc, h = _create_padded(lib, (4, 4, 4), pad)
+        assert rc == 1 and not h.value
+        assert b"negative padding" in lib.vfem_last_error()
+    rc, h = _create_padded(lib, (0, 4, 4), (2, 2))
+    assert rc == 1 and not h.value
+
+
+@pytest.mark.gpu
+def test_failed_padded_create_leaves_nothing_behind():
+    """a create that fails its argument checks must not pad the next simulator of the thread"""
+    import ctypes
+    from ndr_amd import _lib
+    lib = _lib.load()
+    rc, h = _create_padded(lib, (0, 4, 4), (2, 3))
+    assert rc == 1
+    h = ctypes.c_void_p()
+    lo, hi, n = (ctypes.c_double * 3)(0, 0, 0), (ctypes.c_double * 3)(1, 1, 1), (ctypes.c_int64 * 3)(4, 4, 4)
+    _lib.check(lib.vfem_sim_create(ctypes.byref(h), lo, hi, n))
+    try:
+        assert lib.vfem_sim_num_stored_elements(h) == lib.vfem_sim_num_elements(h) == 64
+    finally:
+        lib.vfem_sim_destroy(h)
+    rc, h = _create_padded(lib, (4, 4, 4), (2, 3))
+    assert rc == 0
+    try:
+        assert lib.vfem_sim_num_stored_elements(h) == (4 + 5) * 16 and lib.vfem_sim_num_elements(h) == 64
+    finally:
+        lib.vfem_sim_destroy(h)
+
+
 def test_product_never_imports_oracle():
     for dirpath, _, files in os.walk(os.path.join(ROOT, "ndr_amd")):
         for f in files:
