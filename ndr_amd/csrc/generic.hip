@@ -9,7 +9,7 @@
 // matrices Ke_e (MG.hh:604-669).  The same gather yields S = sum_e (K_e u_e)[node rows] and the diagonal block M, so
 // the operator apply, the residual and the multicoloured block Gauss-Seidel (MG.hh:193-340) share it.  Deterministic:
 // fixed lane ownership and a fixed xor-shuffle reduction tree.
-#include "vfem_host.h"
+#include "mg_cycle.h"
 #include "q2_modes.h"
 
 
@@ -686,7 +686,7 @@ struct vfem_gmg {
     bool l1_virtual = false;           // degree 2: level 1 applies sum_f E_f cK0[f] on the fly, lv[1].Ke is not stored
     std::vector<GLevel> lv;
     GWeights W;
-    DevBuf<double> cK0, phi, Ainv, pr, pd, pAd, ps, scal, scratch;
+    DevBuf<double> cK0, phi, Ainv, pd, pAd, ps, scal, scratch;
     DevBuf<double> tr1, tr2;           // intermediates of the axis-by-axis transfers
     DevBuf<double> c2tab;              // degree-2 hexahedra: c2K0[g][f] = I_g^T cK0[f] I_g as [entry][64] (level 2 straight from the moduli)
     DevBuf<double> l1tab;              // degree-2 hexahedra: cK0 regrouped for k_q2_level1, [ln][m][f][r][c]
@@ -1052,37 +1052,42 @@ static void gmg_update(vfem_gmg *mg, hipStream_t s) {
     mg->operators_valid = true;
 }
 
-// MG.hh:516-553
-static void gmg_vcycle(vfem_gmg *mg, int l, int nsmooth, bool residual_system, hipStream_t s) {
-    GLevel &L = mg->lv[l];
-    if (l == mg->L) { gmg_coarsest(mg, L.b.p, L.x.p, s); return; }
-    GLevel &C = mg->lv[l + 1];
-    g_dirichlet(L.d, L.mask.p, (l == 0 && !residual_system) ? mg->fine->dvals.p : nullptr, L.x.p, s);
-    for (int i = 0; i < nsmooth; ++i) gmg_smooth(mg, l, L.x.p, L.b.p, 1, s);
-    gmg_apply(mg, l, L.x.p, L.b.p, 1, L.r.p, s);
-    gmg_restrict(mg, l, L.r.p, C.b.p, s);
-    C.x.zero(s);
-    gmg_vcycle(mg, l + 1, nsmooth, true, s);
-    gmg_prolong(mg, l, C.x.p, L.x.p, 1, s);
-    for (int i = 0; i < nsmooth; ++i) gmg_smooth(mg, l, L.x.p, L.b.p, mg->symmetric_gs ? 0 : 1, s);
-}
-// MG.hh:486-508
-static void gmg_fmg(vfem_gmg *mg, int l, int nsmooth, bool residual_system, hipStream_t s) {
-    GLevel &L = mg->lv[l];
-    if (l == mg->L) { gmg_coarsest(mg, L.b.p, L.x.p, s); return; }
-    GLevel &C = mg->lv[l + 1];
-    gmg_restrict(mg, l, L.b.p, C.b.p, s);
-    gmg_fmg(mg, l + 1, nsmooth, residual_system, s);
-    gmg_prolong(mg, l, C.x.p, L.x.p, 0, s);
-    gmg_vcycle(mg, l, nsmooth, residual_system, s);
-}
-static void gmg_cycles(vfem_gmg *mg, int num_steps, int nsmooth, bool zero_dirichlet, bool fmg, hipStream_t s) {
-    if (fmg) {
-        gmg_fmg(mg, 0, nsmooth, zero_dirichlet, s);
-        for (int i = 1; i < num_steps; ++i) gmg_vcycle(mg, 0, nsmooth, zero_dirichlet, s);
-    } else
-        for (int i = 0; i < num_steps; ++i) gmg_vcycle(mg, 0, nsmooth, zero_dirichlet, s);
-}
+// how the generic hierarchies launch the steps of mg_cycle.h (work vectors: the levels' own; the CG vectors: the hierarchy's)
+namespace {
+struct GenericOps {
+    vfem_gmg *mg;
+    hipStream_t s;
+    GLevel &lv(int l) const { return mg->lv[l]; }
+
+    int last_level() const { return mg->L; }
+    void last_level_cycle(bool) { gmg_coarsest(mg, b(mg->L), x(mg->L), s); }
+    bool symmetric() const { return mg->symmetric_gs; }
+    double *x(int l) const { return lv(l).x.p; }
+    double *b(int l) const { return lv(l).b.p; }
+    void enforce_dirichlet(int l, bool residual_system, bool) {
+        g_dirichlet(lv(l).d, lv(l).mask.p, (l == 0 && !residual_system) ? mg->fine->dvals.p : nullptr, x(l), s);
+    }
+    void smooth(int l, int forward, int n) { for (int i = 0; i < n; ++i) gmg_smooth(mg, l, x(l), b(l), forward, s); }
+    void residual(int l) { gmg_apply(mg, l, x(l), b(l), 1, lv(l).r.p, s); }
+    void restrict_residual(int l) { gmg_restrict(mg, l, lv(l).r.p, b(l + 1), s); lv(l + 1).x.zero(s); }
+    void restrict_rhs(int l) { gmg_restrict(mg, l, b(l), b(l + 1), s); }
+    void prolong_correction(int l) { gmg_prolong(mg, l, x(l + 1), x(l), 1, s); }
+    bool prolong_start(int l, bool) { gmg_prolong(mg, l, x(l + 1), x(l), 0, s); return false; }
+
+    long long n_dofs() const { return (long long) lv(0).d.N * lv(0).d.nnodes; }
+    mg_cycle::CgWork cg() const { return {n_dofs(), mg->pd.p, mg->pAd.p, mg->scal.p, s}; }
+    double *s_vector(bool preconditioned) const { return preconditioned ? x(0) : mg->ps.p; }
+    void dot(const double *a, const double *b, double *out) { launch_dot(n_dofs(), a, b, mg->scratch.p, out, s); }
+    void initial_residual(const double *x, const double *b, double *r) { gmg_apply(mg, 0, x, b, 1, r, s); }
+    void shift_and_dot_rs(const double *r, double *sv, double *sc) {
+        g_dirichlet(lv(0).d, lv(0).mask.p, nullptr, sv, s);
+        launch_shift_scalar(sc, s);
+        dot(r, sv, sc + 0);
+    }
+    void apply_dot(const double *d, double *Ad, double *out) { gmg_apply(mg, 0, d, nullptr, 2, Ad, s); dot(d, Ad, out); }   // zeroDirichlet(K d)
+    void step_dot(double *x, double *r, const double *d, const double *Ad, double *sc) { launch_pcg_step(n_dofs(), x, r, d, Ad, sc, s); dot(r, r, sc + 3); }
+};
+}  // namespace
 
 extern "C" {
 
@@ -1302,7 +1307,7 @@ static int gmg_create_common(vfem_gmg **out, vfem_gsim *fine, int L, int first_a
     gmg_setup_transfer_tables(mg.get());
     if (first_active == 0) {
         const size_t n0 = (size_t) fine->d.nnodes * N;
-        mg->pr.alloc(n0); mg->pd.alloc(n0); mg->pAd.alloc(n0); mg->ps.alloc(n0);
+        mg->pd.alloc(n0); mg->pAd.alloc(n0); mg->ps.alloc(n0);
     }
     mg->scal.alloc(8); mg->scal.zero(nullptr); mg->scratch.alloc(REDUCE_SCRATCH_DOUBLES);
     VFEM_HIP(hipDeviceSynchronize());
@@ -1405,11 +1410,9 @@ int vfem_gmg_cycle_from_level(vfem_gmg *mg, int level, double *x, const double *
     GLevel &L = mg->lv[level];
     const size_t bytes = (size_t) L.d.nnodes * L.d.N * sizeof(double);
     VFEM_HIP(hipMemcpyAsync(L.b.p, b, bytes, hipMemcpyDeviceToDevice, s));
-    if (fmg) gmg_fmg(mg, level, nsmooth, true, s);
-    else {
-        VFEM_HIP(hipMemcpyAsync(L.x.p, x, bytes, hipMemcpyDeviceToDevice, s));
-        gmg_vcycle(mg, level, nsmooth, true, s);
-    }
+    if (!fmg) VFEM_HIP(hipMemcpyAsync(L.x.p, x, bytes, hipMemcpyDeviceToDevice, s));
+    GenericOps o{mg, s};
+    mg_cycle::cycles(o, level, 1, nsmooth, true, fmg != 0);
     VFEM_HIP(hipMemcpyAsync(x, L.x.p, bytes, hipMemcpyDeviceToDevice, s));
     VFEM_CATCH
 }
@@ -1468,7 +1471,8 @@ int vfem_gmg_solve(vfem_gmg *mg, double *x, const double *f, int num_steps, int 
     const size_t bytes = (size_t) mg->fine->d.nnodes * mg->fine->d.N * sizeof(double);
     VFEM_HIP(hipMemcpyAsync(mg->lv[0].x.p, x, bytes, hipMemcpyDeviceToDevice, s));
     VFEM_HIP(hipMemcpyAsync(mg->lv[0].b.p, f, bytes, hipMemcpyDeviceToDevice, s));
-    gmg_cycles(mg, num_steps, nsmooth, zero_dirichlet != 0, fmg != 0, s);
+    GenericOps o{mg, s};
+    mg_cycle::cycles(o, 0, num_steps, nsmooth, zero_dirichlet != 0, fmg != 0);
     VFEM_HIP(hipMemcpyAsync(x, mg->lv[0].x.p, bytes, hipMemcpyDeviceToDevice, s));
     VFEM_CATCH
 }
@@ -1477,48 +1481,10 @@ int vfem_gmg_pcg(vfem_gmg *mg, double *x, const double *b, int max_iter, double 
     VFEM_TRY
     hipStream_t s = S(stream);
     if (mg->slab || mg->first_active > 0) throw Error("slab / partial hierarchies are solved by the distributed driver");
-    vfem_gsim *sim = mg->fine;
-    const long long nn = sim->d.nnodes, n3 = sim->d.N * nn;
-    const size_t bytes = (size_t) n3 * sizeof(double);
-    double *r = mg->pr.p, *d = mg->pd.p, *Ad = mg->pAd.p, *sv = mg->ps.p, *sc = mg->scal.p;
-    const uint8_t *mask = mg->lv[0].mask.p;
-    g_dirichlet(sim->d, mask, sim->dvals.p, x, s);                       // MG.hh:687-688
+    g_dirichlet(mg->fine->d, mg->lv[0].mask.p, mg->fine->dvals.p, x, s);   // MG.hh:687-688
     gmg_update(mg, s);                                                   // MG.hh:690-691
-    double host_sc[4];
-    launch_dot(n3, b, b, mg->scratch.p, sc + 4, s);
-    gmg_apply(mg, 0, x, b, 1, r, s);                                     // MG.hh:696
-    launch_dot(n3, r, r, mg->scratch.p, sc + 3, s);
-    VFEM_HIP(hipMemcpyAsync(host_sc, sc + 3, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-    VFEM_HIP(hipStreamSynchronize(s));
-    double rr = host_sc[0];
-    const double bb = host_sc[1];
-    int it = 0;
-    while (it < max_iter && rr > tol * tol * bb) {                       // MG.hh:711 (counter started at 0)
-        ++it;
-        if (mg_smoothing == 0) {
-            VFEM_HIP(hipMemcpyAsync(sv, r, bytes, hipMemcpyDeviceToDevice, s));
-        } else {
-            mg->lv[0].x.zero(s);
-            VFEM_HIP(hipMemcpyAsync(mg->lv[0].b.p, r, bytes, hipMemcpyDeviceToDevice, s));
-            gmg_cycles(mg, mg_iterations, mg_smoothing, true, fmg != 0, s);
-            VFEM_HIP(hipMemcpyAsync(sv, mg->lv[0].x.p, bytes, hipMemcpyDeviceToDevice, s));
-        }
-        g_dirichlet(sim->d, mask, nullptr, sv, s);
-        launch_shift_scalar(sc, s);
-        launch_dot(n3, r, sv, mg->scratch.p, sc + 0, s);
-        launch_pcg_direction(n3, sv, d, sc, it == 1, s);
-        gmg_apply(mg, 0, d, nullptr, 2, Ad, s);                          // zeroDirichlet(K d)
-        launch_dot(n3, d, Ad, mg->scratch.p, sc + 2, s);
-        launch_pcg_step(n3, x, r, d, Ad, sc, s);
-        launch_dot(n3, r, r, mg->scratch.p, sc + 3, s);
-        VFEM_HIP(hipMemcpyAsync(host_sc, sc + 3, sizeof(double), hipMemcpyDeviceToHost, s));
-        VFEM_HIP(hipStreamSynchronize(s));
-        rr = host_sc[0];
-        if (!(rr == rr)) throw Error("PCG produced NaN residual");
-        if (residual_cb) residual_cb(cb_user, it, std::sqrt(rr));
-    }
-    if (iters_out) *iters_out = it;
-    if (relres_out) *relres_out = bb > 0 ? std::sqrt(rr / bb) : 0.0;
+    GenericOps o{mg, s};
+    mg_cycle::pcg(o, x, b, max_iter, tol, mg_iterations, mg_smoothing, fmg != 0, residual_cb, cb_user, iters_out, relres_out);
     VFEM_CATCH
 }
 

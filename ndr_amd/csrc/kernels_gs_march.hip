@@ -22,7 +22,7 @@
 //   Recomputed nodes run the same instruction sequence on the same inputs in every tile, so they agree bit for bit.
 // * Out of place.  Tiles read OLD halo values of their neighbours, so a half sweep must not overwrite its input: it reads the
 //   relaxed parity from `uR`, the other parity from `uO` and writes the relaxed planes to `dst` (!= uR); the caller
-//   ping-pongs between the field and one scratch vector (capi.hip: mg_smooth_n), two sweeps end where they began.
+//   ping-pongs between the field and one scratch vector (mg.hip: mg_smooth_n), two sweeps end where they began.
 // * Arithmetic.  One node per LANE, a wave relaxes two rows of the colour (lanes 0-31 / 32-63).  The node row is summed per
 //   NEIGHBOUR: the moduli of the elements that share a neighbour are combined first (sums and differences over the sides:
 //   l1_merged_core.h, the level-1 arithmetic with a single mirror class), 26 x 9 + 63 + 18 multiply-adds and ~100 additions per

@@ -168,7 +168,7 @@ __global__ void __launch_bounds__(256) k_gs_color_mf(Dims d, const double *__res
 // ------------------------------------------------------------------------------------------
 // ------------------------------------------------------------------------------------------
 // Resident coefficients.  For a box voxel with an isotropic tensor K0 has 36 distinct magnitudes (closed form in
-// capi.hip, vfem_sim::update_k0):
+// sim.hip, vfem_sim::update_k0):
 //   same component a:   K0[(n,a),(m,a)] depends on a and on which of the three index bits of n and m agree   -> 3 x 8 values
 //   components a != b:  K0[(n,a),(m,b)] = sign * C,  C chosen by the axis pair, by the agreement of the third axis' bits and by
 //                       whether tau1 = s(n_lo) s(m_hi) equals tau2 = s(n_hi) s(m_lo)  (lo < hi the two axes, s(bit) = +-1);

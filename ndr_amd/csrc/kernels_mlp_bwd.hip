@@ -1,7 +1,7 @@
 // Backward pass of the Fourier-feature MLP at the reference's precision (the reference differentiates networks.MLP in fp32 through
 // torch.autograd, train_xdg.py:282-329, fem.py:125), on the f16 matrix pipe with split operands, no library GEMM.
 //
-// Per voxel chunk the host (capi.hip: mlp_backward_impl) runs
+// Per voxel chunk the host (mlp.hip: mlp_backward_impl) runs
 //   1. the reference-precision forward kernel (kernels_mlp_x3.hip) with `save_act`: post-ReLU activations of every hidden layer as
 //      two fp16 arrays (hi, lo), h = hi + lo, row-major [voxel][k];
 //   2. k_mlp_backward_x3: dL/d(out) -> gradients wrt the pre-activations of every layer, dz (hi, lo), loss-scaled; the products

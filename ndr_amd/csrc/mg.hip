@@ -1,14 +1,11 @@
 // The multigrid hierarchy of the trilinear simulator: creation (levels, coarsened Dirichlet masks, coarsened reference matrices),
 // operator updates, V-cycle / FMG / PCG drivers and the vfem_mg_* entry points of include/vfem.h (the slab solve: mg_slab.hip).
 //
-// Control flow follows the reference (paths relative to the reference checkout):
-//   MultigridSolver ctor (hierarchy, Dirichlet coarsening)   VoxelFEM/MultigridSolver.hh:22-90
-//   vcycle / fullMultigrid / solve / applyPreconditionerInv   VoxelFEM/MultigridSolver.hh:447-553
-//   preconditionedConjugateGradient                           VoxelFEM/MultigridSolver.hh:679-732
-#include "vfem_host.h"
+// The hierarchy follows the reference's MultigridSolver constructor (levels, Dirichlet coarsening: VoxelFEM/MultigridSolver.hh:22-90
+// of the reference checkout); the cycles and the PCG loop are those of mg_cycle.h, launched as TunedOps says.
+#include "mg_cycle.h"
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <memory>
 
@@ -284,40 +281,54 @@ void vfem::update_operators(vfem_mg *mg, hipStream_t s) {
     mg->operators_version = sim->operator_version;
 }
 
-// vcycle, MG.hh:516-553
-void vfem::vcycle(vfem_mg *mg, int l, int nsmooth, bool residual_system, hipStream_t s, bool dirichlet_zeroed) {
-    MgLevel &L = mg->lv[l];
-    if (l == mg->L) { coarsest_solve(mg, L.b.p, L.x.p, s); return; }
-    MgLevel &C = mg->lv[l + 1];
-    if (!(dirichlet_zeroed && residual_system))
-        launch_enforce_dirichlet(L.d.nn, L.maskp, l == 0 ? mg->fine->dvals.p : nullptr, L.x.p, residual_system ? 1 : 0, s);
-    mg_smooth_n(mg, l, L.x.p, L.b.p, 1, nsmooth, s);
-    mg_apply(mg, l, L.x.p, L.b.p, 1, L.r.p, s);                       // computeResidual (Dirichlet zeroed)
-    launch_restrict(C.d, L.d.NX, C.xshift, L.r.p, C.b.p, s, C.x.p);  // ... and the zero initial guess of the coarse level
-    vcycle(mg, l + 1, nsmooth, true, s, true);
-    launch_prolong(C.d, L.d.NX, C.xshift, C.x.p, L.x.p, 1, s);
-    mg_smooth_n(mg, l, L.x.p, L.b.p, mg->symmetric_gs ? 0 : 1, nsmooth, s);
-}
+// how the trilinear hierarchy launches the steps of mg_cycle.h (work vectors: the levels' own; the CG vectors: the hierarchy's)
+namespace {
+struct TunedOps {
+    vfem_mg *mg;
+    hipStream_t s;
+    MgLevel &lv(int l) const { return mg->lv[(size_t) l]; }
 
-// fullMultigrid, MG.hh:486-508
-void vfem::full_multigrid(vfem_mg *mg, int l, int nsmooth, bool residual_system, hipStream_t s) {
-    MgLevel &L = mg->lv[l];
-    if (l == mg->L) { coarsest_solve(mg, L.b.p, L.x.p, s); return; }
-    MgLevel &C = mg->lv[l + 1];
-    launch_restrict(C.d, L.d.NX, C.xshift, L.b.p, C.b.p, s);
-    full_multigrid(mg, l + 1, nsmooth, residual_system, s);
-    launch_prolong(C.d, L.d.NX, C.xshift, C.x.p, L.x.p, 0, s, residual_system ? L.maskp : nullptr);
-    vcycle(mg, l, nsmooth, residual_system, s, residual_system);
-}
-
-// MG::solve on the level-0 work vectors (x[0], b[0] already set), MG.hh:457-471
-static void mg_cycles(vfem_mg *mg, int num_steps, int nsmooth, bool zero_dirichlet, bool fmg, hipStream_t s) {
-    if (fmg) {
-        full_multigrid(mg, 0, nsmooth, zero_dirichlet, s);
-        for (int i = 1; i < num_steps; ++i) vcycle(mg, 0, nsmooth, zero_dirichlet, s);
-    } else {
-        for (int i = 0; i < num_steps; ++i) vcycle(mg, 0, nsmooth, zero_dirichlet, s);
+    int last_level() const { return mg->L; }
+    void last_level_cycle(bool) { coarsest_solve(mg, lv(mg->L).b.p, lv(mg->L).x.p, s); }
+    bool symmetric() const { return mg->symmetric_gs; }
+    double *x(int l) const { return lv(l).x.p; }
+    double *b(int l) const { return lv(l).b.p; }
+    void enforce_dirichlet(int l, bool residual_system, bool dirichlet_zeroed) {
+        if (!(dirichlet_zeroed && residual_system))
+            launch_enforce_dirichlet(lv(l).d.nn, lv(l).maskp, l == 0 ? mg->fine->dvals.p : nullptr, x(l), residual_system ? 1 : 0, s);
     }
+    void smooth(int l, int forward, int n) { mg_smooth_n(mg, l, x(l), b(l), forward, n, s); }
+    void residual(int l) { mg_apply(mg, l, x(l), b(l), 1, lv(l).r.p, s); }                 // computeResidual (Dirichlet zeroed)
+    // ... and the zero initial guess of the coarse level in the same launch
+    void restrict_residual(int l) { launch_restrict(lv(l + 1).d, lv(l).d.NX, lv(l + 1).xshift, lv(l).r.p, b(l + 1), s, x(l + 1)); }
+    void restrict_rhs(int l) { launch_restrict(lv(l + 1).d, lv(l).d.NX, lv(l + 1).xshift, b(l), b(l + 1), s); }
+    void prolong_correction(int l) { launch_prolong(lv(l + 1).d, lv(l).d.NX, lv(l + 1).xshift, x(l + 1), x(l), 1, s); }
+    bool prolong_start(int l, bool residual_system) {
+        launch_prolong(lv(l + 1).d, lv(l).d.NX, lv(l + 1).xshift, x(l + 1), x(l), 0, s, residual_system ? lv(l).maskp : nullptr);
+        return residual_system;
+    }
+    // the vector work between the cycle and the apply is fused: three passes fewer than one kernel per line of MG.hh:713-725 (same
+    // sums in the same order: iterates and residuals are unchanged bit for bit)
+    long long n_dofs() const { return 3 * lv(0).d.nn; }
+    mg_cycle::CgWork cg() const { return {n_dofs(), mg->pd.p, mg->pAd.p, mg->scal.p, s}; }
+    double *s_vector(bool preconditioned) const { return preconditioned ? x(0) : mg->ps.p; }
+    void dot(const double *a, const double *b, double *out) { launch_dot(n_dofs(), a, b, mg->scratch.p, out, s); }
+    void initial_residual(const double *x, const double *b, double *r) { mg_apply(mg, 0, x, b, 1, r, s); }
+    void shift_and_dot_rs(const double *r, double *sv, double *sc) {
+        launch_shift_scalar(sc, s);
+        launch_dot_zero_dirichlet(n_dofs(), r, sv, lv(0).maskp, mg->scratch.p, sc + 0, s);
+    }
+    void apply_dot(const double *d, double *Ad, double *out) {
+        mg_apply(mg, 0, d, nullptr, 0, Ad, s);
+        launch_dot_zero_dirichlet(n_dofs(), d, Ad, lv(0).maskp, mg->scratch.p, out, s);
+    }
+    void step_dot(double *x, double *r, const double *d, const double *Ad, double *sc) { launch_pcg_step_dot(n_dofs(), x, r, d, Ad, sc, mg->scratch.p, sc + 3, s); }
+};
+}  // namespace
+
+void vfem::cycle_from_level(vfem_mg *mg, int l, int nsmooth, bool fmg, hipStream_t s) {
+    TunedOps o{mg, s};
+    mg_cycle::cycles(o, l, 1, nsmooth, true, fmg);
 }
 
 static void finish_mg_create(vfem_mg *mg) {
@@ -604,11 +615,8 @@ int vfem_mg_cycle_from_level(vfem_mg *mg, int level, double *x, const double *b,
     MgLevel &L = mg->lv[(size_t) level];
     const size_t bytes = (size_t) L.d.nn * 3 * sizeof(double);
     VFEM_HIP(hipMemcpyAsync(L.b.p, b, bytes, hipMemcpyDeviceToDevice, s));
-    if (fmg) full_multigrid(mg, level, nsmooth, true, s);
-    else {
-        VFEM_HIP(hipMemcpyAsync(L.x.p, x, bytes, hipMemcpyDeviceToDevice, s));
-        vcycle(mg, level, nsmooth, true, s);
-    }
+    if (!fmg) VFEM_HIP(hipMemcpyAsync(L.x.p, x, bytes, hipMemcpyDeviceToDevice, s));
+    cycle_from_level(mg, level, nsmooth, fmg != 0, s);
     VFEM_HIP(hipMemcpyAsync(x, L.x.p, bytes, hipMemcpyDeviceToDevice, s));
     VFEM_CATCH
 }
@@ -624,7 +632,8 @@ int vfem_mg_solve(vfem_mg *mg, double *x, const double *f, int num_steps, int ns
     const size_t bytes = (size_t) mg->fine->d.nn * 3 * sizeof(double);
     VFEM_HIP(hipMemcpyAsync(mg->lv[0].x.p, x, bytes, hipMemcpyDeviceToDevice, s));
     VFEM_HIP(hipMemcpyAsync(mg->lv[0].b.p, f, bytes, hipMemcpyDeviceToDevice, s));
-    mg_cycles(mg, num_steps, nsmooth, zero_dirichlet != 0, fmg != 0, s);
+    TunedOps o{mg, s};
+    mg_cycle::cycles(o, 0, num_steps, nsmooth, zero_dirichlet != 0, fmg != 0);
     VFEM_HIP(hipMemcpyAsync(x, mg->lv[0].x.p, bytes, hipMemcpyDeviceToDevice, s));
     VFEM_CATCH
 }
@@ -636,52 +645,11 @@ int vfem_mg_pcg(vfem_mg *mg, double *x, const double *b, int max_iter, double to
     hipStream_t s = S(stream);
     vfem_sim *sim = mg->fine;
     if (mg->slab || mg->first_active != 0) throw Error("this hierarchy is driven by the distributed solver");
-    const long long nn = sim->d.nn, n3 = 3 * nn;
-    const size_t bytes = (size_t) n3 * sizeof(double);
-    // the residual lives in the level-0 right-hand-side buffer of the hierarchy and the preconditioned residual is read from
-    // its level-0 iterate: the cycle never writes b[0], so neither vector has to be copied in or out (2 x 3.2 GB per iteration
-    // at 512^3)
-    double *r = mg->lv[0].b.p, *d = mg->pd.p, *Ad = mg->pAd.p, *sc = mg->scal.p;
-    double *sv = mg_smoothing == 0 ? mg->ps.p : mg->lv[0].x.p;
-    const uint8_t *mask = mg->lv[0].maskp;
-
-    launch_enforce_dirichlet(nn, mask, sim->dvals.p, x, 0, s);          // MG.hh:687-688
-    update_operators(mg, s);                                            // MG.hh:690-691
+    launch_enforce_dirichlet(sim->d.nn, mg->lv[0].maskp, sim->dvals.p, x, 0, s);    // MG.hh:687-688
+    update_operators(mg, s);                                                      // MG.hh:690-691
     ScopedTimer tm("CG Iterations");
-    double host_sc[4];
-    launch_dot(n3, b, b, mg->scratch.p, sc + 4, s);                     // ||b||^2
-    mg_apply(mg, 0, x, b, 1, r, s);                                     // r = b - K x, Dirichlet zeroed (MG.hh:696)
-    launch_dot(n3, r, r, mg->scratch.p, sc + 3, s);
-    VFEM_HIP(hipMemcpyAsync(host_sc, sc + 3, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-    VFEM_HIP(hipStreamSynchronize(s));
-    double rr = host_sc[0];
-    const double bb = host_sc[1];
-    int it = 0;
-    while (it < max_iter && rr > tol * tol * bb) {                      // MG.hh:711 (counter started at 0)
-        ++it;
-        // s = M^{-1} r  (applyPreconditionerInv, MG.hh:476-479)
-        if (mg_smoothing == 0) {
-            VFEM_HIP(hipMemcpyAsync(sv, r, bytes, hipMemcpyDeviceToDevice, s));
-        } else {
-            if (!fmg) mg->lv[0].x.zero(s);          // full multigrid overwrites the iterate of every level (prolongation, MG.hh:500)
-            mg_cycles(mg, mg_iterations, mg_smoothing, true, fmg != 0, s);
-        }
-        // the vector work between the cycle and the apply, three passes fewer than one kernel per line of MG.hh:713-725 (same
-        // sums in the same order: iterates and residuals are unchanged bit for bit)
-        launch_shift_scalar(sc, s);                                     // rMr_old = rMr
-        launch_dot_zero_dirichlet(n3, r, sv, mask, mg->scratch.p, sc + 0, s);   // s = zeroDirichlet(s); rMr = r . s
-        launch_pcg_direction(n3, sv, d, sc, it == 1, s);
-        mg_apply(mg, 0, d, nullptr, 0, Ad, s);                          // Ad = K d
-        launch_dot_zero_dirichlet(n3, d, Ad, mask, mg->scratch.p, sc + 2, s);   // Ad = zeroDirichlet(Ad); d . Ad
-        launch_pcg_step_dot(n3, x, r, d, Ad, sc, mg->scratch.p, sc + 3, s);      // x += alpha d, r -= alpha Ad, ||r||^2
-        VFEM_HIP(hipMemcpyAsync(host_sc, sc + 3, sizeof(double), hipMemcpyDeviceToHost, s));
-        VFEM_HIP(hipStreamSynchronize(s));
-        rr = host_sc[0];
-        if (!(rr == rr)) throw Error("PCG produced NaN residual");
-        if (residual_cb) residual_cb(cb_user, it, std::sqrt(rr));
-    }
-    if (iters_out) *iters_out = it;
-    if (relres_out) *relres_out = bb > 0 ? std::sqrt(rr / bb) : 0.0;
+    TunedOps o{mg, s};
+    mg_cycle::pcg(o, x, b, max_iter, tol, mg_iterations, mg_smoothing, fmg != 0, residual_cb, cb_user, iters_out, relres_out);
     VFEM_CATCH
 }
 

@@ -1,7 +1,5 @@
 // The slab-decomposed MG-PCG solve of the trilinear hierarchy (vfem_mg_pcg_slab of include/vfem.h); the hierarchy itself: mg.hip.
-#include "vfem_host.h"
-
-#include <cmath>
+#include "mg_cycle.h"
 
 using namespace vfem;
 
@@ -10,15 +8,16 @@ using namespace vfem;
 // iteration measured by the rank proxy (profiles/r04_rank_proxy_python_driver.json) against the 2.0 / 12 ms a rank has at 256^3 /
 // 512^3 on eight ranks.  Here a rank's whole solve is ONE call; the two things only the host language can do -- refresh ghost planes
 // from the neighbours, sum a few doubles over the ranks (torch.distributed: RCCL on the GPU box, gloo in the tests) -- are callbacks.
-// Control flow = DistributedMGSolver's (vcycle / full_multigrid / smooth with the parity-aware, boundary-planes-first exchanges),
-// itself MG.hh:486-553, 679-732; all work vectors belong to the caller, so a callback can map a pointer back to its own array.
+// Control flow = DistributedMGSolver's: the cycles and the PCG loop of mg_cycle.h, with DistDriver as their operations type (smooth
+// with the parity-aware, boundary-planes-first exchanges); all work vectors belong to the caller, so a callback can map a pointer
+// back to its own array.
 namespace {
 struct DistDriver {
     vfem_mg *loc, *rep;
     int T, rank, world, nsmooth;
     bool overlap;
     const vfem_dist_level *g;
-    double *xT, *bT;
+    double *xT, *bT, *work_d, *work_Ad, *scalars;
     vfem_halo_fn halo_fn;
     vfem_allreduce_fn allreduce_fn;
     void *user;
@@ -81,35 +80,43 @@ struct DistDriver {
         VFEM_HIP(hipMemcpyAsync(bT + (G.xoffn + lo) * per, G.b + lo * per, (size_t) ((hi - lo) * per) * sizeof(double), hipMemcpyDeviceToDevice, s));
         allreduce(bT, (long long) R.d.nn * 3);
         VFEM_HIP(hipMemcpyAsync(R.b.p, bT, bytes, hipMemcpyDeviceToDevice, s));
-        if (fmg) full_multigrid(rep, T, nsmooth, true, s);
-        else { R.x.zero(s); vcycle(rep, T, nsmooth, true, s); }
+        if (!fmg) R.x.zero(s);
+        cycle_from_level(rep, T, nsmooth, fmg, s);
         VFEM_HIP(hipMemcpyAsync(G.x, R.x.p + G.xoffn * per, (size_t) (G.n_planes * per) * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
-    void vcycle_d(int l) {
-        if (l == T) { coarse_cycle(false); return; }
-        const vfem_dist_level &G = g[l], &C = g[l + 1];
-        MgLevel &L = loc->lv[(size_t) l], &LC = loc->lv[(size_t) l + 1];
-        launch_zero_dirichlet(L.d.nn, L.maskp, G.x, s);                  // residual system
-        for (int i = 0; i < nsmooth; ++i) smooth(l, G.x, G.b, 1);
-        mg_apply(loc, l, G.x, G.b, 1, G.r, s);
-        halo(l, G.r);
-        launch_restrict(LC.d, L.d.NX, LC.xshift, G.r, C.b, s, C.x);      // ... and the zero initial guess of the coarse level
-        vcycle_d(l + 1);
-        launch_prolong(LC.d, L.d.NX, LC.xshift, C.x, G.x, 1, s);
-        halo(l, G.x);
-        for (int i = 0; i < nsmooth; ++i) smooth(l, G.x, G.b, loc->symmetric_gs ? 0 : 1);
+    // ---- what mg_cycle.h asks for: the levels 0 .. T - 1 of the slabs, level T the replicated cycle; an exchange follows whatever
+    // a neighbour reads next (residual, prolongations) and precedes what reads ghost planes (right-hand-side restriction, K d)
+    MgLevel &lv(int l) const { return loc->lv[(size_t) l]; }
+    int last_level() const { return T; }
+    void last_level_cycle(bool fmg) { coarse_cycle(fmg); }
+    bool symmetric() const { return loc->symmetric_gs; }
+    double *x(int l) const { return g[l].x; }
+    double *b(int l) const { return g[l].b; }
+    void enforce_dirichlet(int l, bool, bool) { launch_zero_dirichlet(lv(l).d.nn, lv(l).maskp, x(l), s); }   // residual systems only
+    void smooth(int l, int forward, int n) { for (int i = 0; i < n; ++i) smooth(l, x(l), b(l), forward); }
+    void residual(int l) { mg_apply(loc, l, x(l), b(l), 1, g[l].r, s); halo(l, g[l].r); }
+    // ... and the zero initial guess of the coarse level in the same launch
+    void restrict_residual(int l) { launch_restrict(lv(l + 1).d, lv(l).d.NX, lv(l + 1).xshift, g[l].r, b(l + 1), s, x(l + 1)); }
+    void restrict_rhs(int l) { halo(l, b(l)); launch_restrict(lv(l + 1).d, lv(l).d.NX, lv(l + 1).xshift, b(l), b(l + 1), s); }
+    void prolong_correction(int l) { launch_prolong(lv(l + 1).d, lv(l).d.NX, lv(l + 1).xshift, x(l + 1), x(l), 1, s); halo(l, x(l)); }
+    bool prolong_start(int l, bool) { launch_prolong(lv(l + 1).d, lv(l).d.NX, lv(l + 1).xshift, x(l + 1), x(l), 0, s); halo(l, x(l)); return false; }
+
+    long long n_dofs() const { return 3 * lv(0).d.nn; }
+    mg_cycle::CgWork cg() const { return {n_dofs(), work_d, work_Ad, scalars, s}; }
+    double *s_vector(bool) const { return x(0); }
+    void initial_residual(double *x, const double *b, double *r) { halo(0, x); mg_apply(loc, 0, x, b, 1, r, s); }
+    void shift_and_dot_rs(const double *r, double *sv, double *sc) {
+        launch_zero_dirichlet(lv(0).d.nn, lv(0).maskp, sv, s);
+        launch_shift_scalar(sc, s);                                     // rMr_old = rMr
+        dot(r, sv, sc + 0);
     }
-    void fmg_d(int l) {
-        if (l == T) { coarse_cycle(true); return; }
-        const vfem_dist_level &G = g[l], &C = g[l + 1];
-        MgLevel &L = loc->lv[(size_t) l], &LC = loc->lv[(size_t) l + 1];
-        halo(l, G.b);
-        launch_restrict(LC.d, L.d.NX, LC.xshift, G.b, C.b, s);
-        fmg_d(l + 1);
-        launch_prolong(LC.d, L.d.NX, LC.xshift, C.x, G.x, 0, s);
-        halo(l, G.x);
-        vcycle_d(l);
+    void apply_dot(double *d, double *Ad, double *out) {
+        halo(0, d);
+        mg_apply(loc, 0, d, nullptr, 0, Ad, s);
+        launch_zero_dirichlet(lv(0).d.nn, lv(0).maskp, Ad, s);
+        dot(d, Ad, out);
     }
+    void step_dot(double *x, double *r, const double *d, const double *Ad, double *sc) { launch_pcg_step(n_dofs(), x, r, d, Ad, sc, s); dot(r, r, sc + 3); }
 };
 }  // namespace
 extern "C" {
@@ -130,56 +137,12 @@ int vfem_mg_pcg_slab(vfem_mg *local, vfem_mg *replicated, int first_replicated_l
         if (levels[l].n_planes != L.d.NX || levels[l].plane_nodes != (int64_t) L.d.NY * L.d.NZ) throw Error("vfem_mg_pcg_slab: level geometry does not match the hierarchy");
         if (!levels[l].x || !levels[l].b || (l < T && !levels[l].r)) throw Error("vfem_mg_pcg_slab: work vector missing");
     }
-    DistDriver D{local, replicated, T, rank, world, mg_smoothing, overlap_sweeps != 0, levels, replicated_x, replicated_b, halo, allreduce, cb_user, S(stream)};
-    hipStream_t s = D.s;
-    const vfem_dist_level &G0 = levels[0];
-    const MgLevel &L0 = local->lv[0];
-    const long long nn = L0.d.nn, n3 = 3 * nn;
-    const size_t bytes = (size_t) n3 * sizeof(double);
-    // as in vfem_mg_pcg the residual lives in the level-0 right-hand side of the cycle and the preconditioned residual is its iterate
-    double *r = G0.b, *sv = G0.x, *d = work_d, *Ad = work_Ad, *sc = scalars;
-    launch_zero_dirichlet(nn, L0.maskp, x, s);                           // (zero Dirichlet values only: DistributedMGSolver.pcg)
-    update_operators(local, s);                                          // no-ops when the caller has done it (sharded densities: it must)
-    update_operators(replicated, s);
-    double host_sc[2];
-    D.dot(b, b, sc + 4);
-    D.halo(0, x);
-    mg_apply(local, 0, x, b, 1, r, s);
-    D.dot(r, r, sc + 3);
-    VFEM_HIP(hipMemcpyAsync(host_sc, sc + 3, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-    VFEM_HIP(hipStreamSynchronize(s));
-    double rr = host_sc[0];
-    const double bb = host_sc[1];
-    int it = 0;
-    while (it < max_iter && rr > tol * tol * bb) {
-        ++it;
-        if (mg_smoothing == 0) {
-            VFEM_HIP(hipMemcpyAsync(sv, r, bytes, hipMemcpyDeviceToDevice, s));
-        } else if (fmg) {
-            D.fmg_d(0);
-            for (int i = 1; i < mg_iterations; ++i) D.vcycle_d(0);
-        } else {
-            VFEM_HIP(hipMemsetAsync(sv, 0, bytes, s));
-            for (int i = 0; i < mg_iterations; ++i) D.vcycle_d(0);
-        }
-        launch_zero_dirichlet(nn, L0.maskp, sv, s);
-        launch_shift_scalar(sc, s);                                     // rMr_old = rMr
-        D.dot(r, sv, sc + 0);
-        launch_pcg_direction(n3, sv, d, sc, it == 1, s);
-        D.halo(0, d);
-        mg_apply(local, 0, d, nullptr, 0, Ad, s);
-        launch_zero_dirichlet(nn, L0.maskp, Ad, s);
-        D.dot(d, Ad, sc + 2);
-        launch_pcg_step(n3, x, r, d, Ad, sc, s);                         // x += alpha d, r -= alpha Ad
-        D.dot(r, r, sc + 3);
-        VFEM_HIP(hipMemcpyAsync(host_sc, sc + 3, sizeof(double), hipMemcpyDeviceToHost, s));
-        VFEM_HIP(hipStreamSynchronize(s));
-        rr = host_sc[0];
-        if (!(rr == rr)) throw Error("PCG produced NaN residual");
-        if (residual_cb) residual_cb(residual_user, it, std::sqrt(rr));
-    }
-    if (iters_out) *iters_out = it;
-    if (relres_out) *relres_out = bb > 0 ? std::sqrt(rr / bb) : 0.0;
+    DistDriver D{local, replicated, T, rank, world, mg_smoothing, overlap_sweeps != 0, levels, replicated_x, replicated_b, work_d, work_Ad, scalars,
+                 halo, allreduce, cb_user, S(stream)};
+    launch_zero_dirichlet(local->lv[0].d.nn, local->lv[0].maskp, x, D.s);  // (zero Dirichlet values only: DistributedMGSolver.pcg)
+    update_operators(local, D.s);                                          // no-ops when the caller has done it (sharded densities: it must)
+    update_operators(replicated, D.s);
+    mg_cycle::pcg(D, x, b, max_iter, tol, mg_iterations, mg_smoothing, fmg != 0, residual_cb, residual_user, iters_out, relres_out);
     VFEM_CATCH
 }
 

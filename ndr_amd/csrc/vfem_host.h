@@ -16,9 +16,9 @@ static inline hipStream_t S(void *s) { return (hipStream_t) s; }
 
 namespace vfem {
 
-// timer registry (BENCHMARK_* of MeshFEM GlobalBenchmark.hh / Timer.hh): host wall time + call count per named section (capi.hip);
-// sections enclosing only asynchronous launches measure enqueue time unless the caller synchronises (the PCG loop does, once
-// per iteration).
+// timer registry (BENCHMARK_* of MeshFEM GlobalBenchmark.hh / Timer.hh): host wall time + call count per named section (the
+// registry: capi.hip); sections enclosing only asynchronous launches measure enqueue time unless the caller synchronises (the PCG
+// loop of mg_cycle.h does, once per iteration).
 void timer_add(const char *name, double seconds);
 struct ScopedTimer {
     const char *name;
@@ -50,9 +50,8 @@ void mg_smooth(vfem_mg *mg, int l, double *u, const double *b, int forward, hipS
 // one colour group (half sweep `half` of the sweep order) of level 0 by the marching kernel, result back in u; false: not available
 bool mg_smooth_half(vfem_mg *mg, int l, double *u, const double *b, int forward, int half, hipStream_t s, int plane_lo = 0, int plane_hi = -1);
 void update_operators(vfem_mg *mg, hipStream_t s);
-// dirichlet_zeroed: the level's iterate has zeros at the Dirichlet components already (just zeroed by the restriction of the level
-// above, or interpolated with the mask by full_multigrid), which is all the residual system asks for (MG.hh:521-523)
-void vcycle(vfem_mg *mg, int l, int nsmooth, bool residual_system, hipStream_t s, bool dirichlet_zeroed = false);
-void full_multigrid(vfem_mg *mg, int l, int nsmooth, bool residual_system, hipStream_t s);
+// one V-cycle (on the iterate x[l]) or one full-multigrid cycle of the residual system b[l] from level l on: what the slab driver
+// runs its replicated levels with
+void cycle_from_level(vfem_mg *mg, int l, int nsmooth, bool fmg, hipStream_t s);
 
 }  // namespace vfem

@@ -317,7 +317,7 @@ class GenericMG:
 
     def apply_preconditioner_inv(self, r, num_steps, nsmooth, fmg):
         if nsmooth == 0:
-            return r                                                  # MG.hh:476-479
+            return r.copy()                                           # MG.hh:476-479 (by value: the first direction must not alias r)
         return self.solve(np.zeros_like(r), r, num_steps, nsmooth, True, True, fmg).copy()
 
     def pcg(self, u, b, max_iter, tol, mg_iterations=1, mg_smoothing=1, fmg=False):

@@ -263,6 +263,18 @@ def test_pcg_parameterisations_and_callback_match_oracle(mgit, nsm, fmg, sym, le
         assert np.linalg.norm(o.apply_k(ug)[o.dmask == 0] - f[o.dmask == 0]) <= 1.01 * tol * np.linalg.norm(f)
 
 
+def test_unpreconditioned_cg_matches_oracle():
+    """mgSmoothingIterations = 0 (MG.hh:476-479): plain CG, cut off at 20 iterations long before it converges"""
+    o, t, omg, tmg = _mg_pair((32, 16, 16), ([0, 0, 0], [2, 1, 1]), BC_CANTILEVER, 2, "proxy")
+    f = o.build_load_vector()
+    uo = omg.pcg(np.zeros_like(f), f, 20, 1e-12, 1, 0, False)
+    ug = tmg.preconditionedConjugateGradient(np.zeros_like(f), f, 20, 1e-12, None, 1, 0, False)
+    assert tmg.last_iterations == 20 and omg.last_iters == 20
+    err = np.abs(ug.reshape(uo.shape) - uo).max() / np.abs(uo).max()
+    print("unpreconditioned CG, 20 iterations: max|x - x_oracle| / max|x_oracle| = %.3e" % err)
+    assert err < 1e-7
+
+
 def test_apply_k_at_the_headline_size_512_cubed():
     """k_apply_dma at the size the metric is quoted on (9 z-tiles + strip, 8 x-chunks): against the independent gather kernel,
     symmetry, linearity, rigid translations in the null space"""
