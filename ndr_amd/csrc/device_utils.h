@@ -27,6 +27,15 @@ __device__ __forceinline__ const T *launder_uniform(const T *p) {
 }
 
 
+// a double from its two 32-bit halves (what a buffer load, a DPP move or a readlane hands back)
+__device__ __forceinline__ double mkd(unsigned lo, unsigned hi) { return __longlong_as_double(((unsigned long long) hi << 32) | lo); }
+
+// 16 bytes per lane from global memory straight into LDS (global_load_lds_dwordx4): no register in between
+__device__ __forceinline__ void glds16(const void *g, void *l) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) g,
+                                     (__attribute__((address_space(3))) void *) l, 16, 0, 0);
+}
+
 typedef double d8_t __attribute__((ext_vector_type(8)));
 
 // Wave-uniform coefficient tables are read with explicit scalar loads issued exactly where they are consumed (the
@@ -69,7 +78,7 @@ __device__ __forceinline__ double lane_below(double v) {
     const unsigned long long b = __double_as_longlong(v);
     const unsigned lo = __builtin_amdgcn_update_dpp(0u, (unsigned) (b & 0xffffffffull), 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
     const unsigned hi = __builtin_amdgcn_update_dpp(0u, (unsigned) (b >> 32), 0x138, 0xf, 0xf, true);
-    return __longlong_as_double(((unsigned long long) hi << 32) | lo);
+    return mkd(lo, hi);
 }
 
 
@@ -78,7 +87,7 @@ __device__ __forceinline__ double lane_above(double v) {
     const unsigned long long b = __double_as_longlong(v);
     const unsigned lo = __builtin_amdgcn_update_dpp(0u, (unsigned) (b & 0xffffffffull), 0x130 /* wave_shl:1 */, 0xf, 0xf, true);
     const unsigned hi = __builtin_amdgcn_update_dpp(0u, (unsigned) (b >> 32), 0x130, 0xf, 0xf, true);
-    return __longlong_as_double(((unsigned long long) hi << 32) | lo);
+    return mkd(lo, hi);
 }
 
 // component-sequential 3x3 solve of m_smoothNode (MG.hh:254-264)

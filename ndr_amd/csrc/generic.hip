@@ -10,6 +10,7 @@
 // the operator apply, the residual and the multicoloured block Gauss-Seidel (MG.hh:193-340) share it.  Deterministic:
 // fixed lane ownership and a fixed xor-shuffle reduction tree.
 #include "mg_cycle.h"
+#include "device_utils.h"
 #include "q2_modes.h"
 
 
@@ -115,7 +116,7 @@ __device__ __forceinline__ void g_gather(const GDims &d, const double *__restric
                         const unsigned long long bits = __double_as_longlong(src);
                         const unsigned lo = __builtin_amdgcn_readlane((unsigned) (bits & 0xffffffffull), qd & 63);
                         const unsigned hi = __builtin_amdgcn_readlane((unsigned) (bits >> 32), qd & 63);
-                        const double kd = __longlong_as_double(((unsigned long long) hi << 32) | lo);
+                        const double kd = mkd(lo, hi);
                         M[3 * r + c] = fma(sc, kd, M[3 * r + c]);
                     }
                 }
@@ -202,7 +203,7 @@ __device__ __forceinline__ void g_gather_fixed3(const GDims &d, const double *__
                         const unsigned long long bits = __double_as_longlong(src);
                         const unsigned lo32 = __builtin_amdgcn_readlane((unsigned) (bits & 0xffffffffull), qd & 63);
                         const unsigned hi32 = __builtin_amdgcn_readlane((unsigned) (bits >> 32), qd & 63);
-                        const double kd = __longlong_as_double(((unsigned long long) hi32 << 32) | lo32);
+                        const double kd = mkd(lo32, hi32);
                         M[3 * r + c] = fma(sc, kd, M[3 * r + c]);
                     }
                 }

@@ -69,11 +69,6 @@ using Strip = Cfg<4, 16>;
 
 struct DmArgs2 { double v[36]; };
 
-__device__ __forceinline__ void glds16(const void *g, void *l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) g,
-                                     (__attribute__((address_space(3))) void *) l, 16, 0, 0);
-}
-
 // RES: out = b - K u with 0 at the fixed components (the residual of the V-cycle) instead of K u: right-hand side and mask of the
 // node a thread emits are requested one phase ahead, before the arithmetic of the plane in between
 template <int EXP, class C, bool RES = false, bool LX = false>

@@ -73,12 +73,6 @@ struct GsMarchArgs {
 typedef double d2a_t __attribute__((ext_vector_type(2), aligned(16)));
 typedef unsigned int u4q_t __attribute__((ext_vector_type(4)));
 typedef unsigned int u2q_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double mkd(unsigned lo, unsigned hi) { return __longlong_as_double(((unsigned long long) hi << 32) | lo); }
-
-__device__ __forceinline__ void gsm_glds16(const void *g, void *l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *) g,
-                                     (__attribute__((address_space(3))) void *) l, 16, 0, 0);
-}
 // The nine doubles of a node window start at an index whose parity depends on the row and the plane (the alignment shift of the
 // staged image).  Ten doubles from the 16-byte-aligned index at or below it are read instead, always as five 16-byte reads in the
 // same registers whatever the parity; the consumer then indexes w[off + j] with off = the parity, a compile-time constant.
@@ -163,7 +157,7 @@ __global__ void __launch_bounds__(64 * (gsm::CW + 1)) k_gs_march_mf0(GsMarchArgs
                 // at all, it is no faster: 5.84 / 0.95).
                 const char *pp = reinterpret_cast<const char *>(buf + 3LL * i * plane) - 32;
 #pragma unroll
-                for (int t = 0; t < U_INSTR; ++t) gsm_glds16(pp + (par0 ? dm1[t] : dm0[t]), slot + 1024 * t);
+                for (int t = 0; t < U_INSTR; ++t) glds16(pp + (par0 ? dm1[t] : dm0[t]), slot + 1024 * t);
                 return;
             }
             const double *pb = buf + 3LL * i * plane - 3;               // (the bias of ugo)
@@ -171,7 +165,7 @@ __global__ void __launch_bounds__(64 * (gsm::CW + 1)) k_gs_march_mf0(GsMarchArgs
             for (int t = 0; t < U_INSTR; ++t) {
                 const char *g = reinterpret_cast<const char *>(pb + (long long) (ugo[t] >> 1) - (long long) ((par0 + (int) (ugo[t] & 1)) & 1));
                 g = g > last ? last : (g < first ? first : g);
-                gsm_glds16(g, slot + 1024 * t);
+                glds16(g, slot + 1024 * t);
             }
         };
         issueU(0); issueU(1); issueU(2);

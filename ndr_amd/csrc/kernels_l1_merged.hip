@@ -31,7 +31,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const double *base,
     const double *p = base + (long long) (ok ? plane : 0) * plane_doubles;
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<double *>(p), 0, ok ? (int) (plane_doubles * 8) : 0, 0x00020000);
 }
-__device__ __forceinline__ double mk(unsigned lo, unsigned hi) { return __longlong_as_double(((unsigned long long) hi << 32) | lo); }
 
 // the 3 x 3 nodes (j + o_y, k + o_z) of one x-plane: un[o_y + 1][3 (o_z + 1) + c]
 __device__ __forceinline__ void load_nodes(__amdgpu_buffer_rsrc_t r, const Dims &d, int j, int k, double (&un)[3][9]) {
@@ -48,9 +47,9 @@ __device__ __forceinline__ void load_nodes(__amdgpu_buffer_rsrc_t r, const Dims 
             const u4_t v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
             const u2_t w = __builtin_amdgcn_raw_buffer_load_b64(r, off + 16, 0, 0);
 #endif
-            un[oy + 1][3 * (oz + 1) + 0] = mk(v.x, v.y);
-            un[oy + 1][3 * (oz + 1) + 1] = mk(v.z, v.w);
-            un[oy + 1][3 * (oz + 1) + 2] = mk(w.x, w.y);
+            un[oy + 1][3 * (oz + 1) + 0] = mkd(v.x, v.y);
+            un[oy + 1][3 * (oz + 1) + 1] = mkd(v.z, v.w);
+            un[oy + 1][3 * (oz + 1) + 2] = mkd(w.x, w.y);
         }
 }
 // The moduli of a node group in LDS: sE[fine x-plane p_x][4 p_y + p_z][lane] (32 KB per workgroup, every lane reads back only what it
@@ -89,8 +88,8 @@ __device__ __forceinline__ void stage_moduli(__amdgpu_buffer_rsrc_t r, const uns
     for (int py = 0; py < 4; ++py)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            plane[4 * py + 2 * h][lane] = mk(v[py][h].x, v[py][h].y);
-            plane[4 * py + 2 * h + 1][lane] = mk(v[py][h].z, v[py][h].w);
+            plane[4 * py + 2 * h][lane] = mkd(v[py][h].x, v[py][h].y);
+            plane[4 * py + 2 * h + 1][lane] = mkd(v[py][h].z, v[py][h].w);
         }
 }
 

@@ -22,27 +22,17 @@
 #include <hip/hip_fp16.h>
 
 #include "mlp_args.h"
+#include "mlp_device.h"
 
 namespace vfem {
 
-typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
-typedef float f16_t __attribute__((ext_vector_type(16)));
+using namespace mlp;
 
 constexpr int MLP_TM = 128;                 // voxels per block
 constexpr int MLP_MAXN = 512;               // max hidden width
 constexpr int MLP_HSTRIDE = MLP_MAXN + 8;   // halves per activation row (16-byte pad)
 constexpr int MLP_KC = 64;                  // feature chunk
 constexpr int MLP_FSTRIDE = MLP_KC + 8;     // halves per feature row (16-byte pad)
-
-__device__ __forceinline__ void voxel_coord(const MlpArgs &a, long long v, float x[3]) {
-    if (a.coords) { x[0] = a.coords[3 * v]; x[1] = a.coords[3 * v + 1]; x[2] = a.coords[3 * v + 2]; return; }
-    v += a.v_offset;
-    const long long k = v % a.gn[2], j = (v / a.gn[2]) % a.gn[1], i = v / ((long long) a.gn[2] * a.gn[1]);
-    x[0] = a.glo[0] + a.gstep[0] * (float) i;
-    x[1] = a.glo[1] + a.gstep[1] * (float) j;
-    x[2] = a.glo[2] + a.gstep[2] * (float) k;
-}
 
 // Weight (A operand) fragments are prefetched MLP_PD k-steps ahead in a register ring: a fragment is one 16-byte load from
 // the L2-resident weight matrix, whose latency (~600 cycles) is several times the 256 MFMA cycles of a k-step, so without
@@ -141,7 +131,7 @@ __global__ void __launch_bounds__(512) k_mlp_forward(MlpArgs a) {
 
     if (tid < MLP_TM) {
         float x[3] = {0.f, 0.f, 0.f};
-        if (v0 + tid < a.nvox) voxel_coord(a, v0 + tid, x);
+        if (v0 + tid < a.nvox) voxel_xyz(a, v0 + tid, x);
         xc[3 * tid] = x[0]; xc[3 * tid + 1] = x[1]; xc[3 * tid + 2] = x[2];
     }
     __syncthreads();
@@ -388,16 +378,6 @@ void launch_f32_to_f16_frag(int N, int K, int transposed, const float *in, void 
     if (N % 32 || K % 16) throw Error("fragment-order weights need N % 32 == 0 and K % 16 == 0");
     long long g = ((long long) N * K + 255) / 256; if (g > 4096) g = 4096; if (g < 1) g = 1;
     k_f32_to_f16_frag<<<dim3((unsigned) g), dim3(256), 0, s>>>(N, K, transposed, in, (_Float16 *) out);
-    VFEM_HIP(hipGetLastError());
-}
-
-__global__ void k_f32_to_f16(long long n, const float *__restrict__ in, _Float16 *__restrict__ out) {
-    for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long) gridDim.x * blockDim.x)
-        out[i] = (_Float16) in[i];
-}
-void launch_f32_to_f16(long long n, const float *in, void *out, hipStream_t s) {
-    long long g = (n + 255) / 256; if (g > 4096) g = 4096; if (g < 1) g = 1;
-    k_f32_to_f16<<<dim3((unsigned) g), dim3(256), 0, s>>>(n, in, (_Float16 *) out);
     VFEM_HIP(hipGetLastError());
 }
 

@@ -21,59 +21,18 @@
 #include <hip/hip_fp16.h>
 
 #include "mlp_args.h"
+#include "mlp_device.h"
 
 namespace vfem {
 
-namespace bw {
-typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
-typedef float f16_t __attribute__((ext_vector_type(16)));
+using namespace mlp;      // (mlp_device.h: what this pass must share with the forward kernels)
+
 typedef __fp16 hf4_t __attribute__((__vector_size__(4 * sizeof(__fp16))));
-constexpr int TM = 64, MAXN = 512, HS = MAXN + 8;
-constexpr float LO_SCALE = 2048.f, LO_INV = 1.f / 2048.f;
-__device__ __forceinline__ void split_scaled(float x, _Float16 &hi, _Float16 &lo) {
-    hi = (_Float16) x;
-    lo = (_Float16) ((x - (float) hi) * LO_SCALE);
-}
-// (the pair of x3::unscale_lo in kernels_mlp_x3.hip: same value for the same half)
-__device__ __forceinline__ _Float16 unscale_lo(_Float16 ls) {
-    const float f = (float) ls;
-    _Float16 u = (_Float16) (f * LO_INV);
-    if ((float) u == 0.f && f != 0.f) u = (_Float16) (f > 0.f ? 5.9604645e-8f : -5.9604645e-8f);
-    return u;
-}
+// halves of the weight gradient's regenerated features: the low half unscaled (see 3. above)
 __device__ __forceinline__ void split_plain(float x, _Float16 &hi, _Float16 &lo) {
     hi = (_Float16) x;
     lo = (_Float16) (x - (float) hi);
 }
-// the pair of sincos_f32 in kernels_mlp_x3.hip (same constants, same order of operations: the features the weight gradient sees are
-// bit for bit the ones the forward pass multiplied)
-__device__ __forceinline__ void sincos_f32(float t, float &sn, float &cs) {
-    const float n = __builtin_rintf(t * 0.636619772367581343f);
-    float y = fmaf(-n, 1.5707963705062866f, t);
-    y = fmaf(-n, -4.371138828673793e-08f, y);
-    y = fmaf(-n, -1.7763568394002505e-15f, y);
-    const float z = y * y;
-    float ps = fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f);
-    ps = fmaf(ps, z, -1.6666654611e-1f);
-    const float s = fmaf(ps * z, y, y);
-    float pc = fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f);
-    pc = fmaf(pc, z, 4.166664568298827e-2f);
-    const float c = fmaf(z * z, pc, fmaf(-0.5f, z, 1.0f));
-    const int q = (int) n;
-    const float a = (q & 1) ? c : s, b = (q & 1) ? s : c;
-    sn = (q & 2) ? -a : a;
-    cs = ((q + 1) & 2) ? -b : b;
-}
-__device__ __forceinline__ void voxel_xyz(const MlpArgs &a, long long v, float x[3]) {
-    if (a.coords) { x[0] = a.coords[3 * v]; x[1] = a.coords[3 * v + 1]; x[2] = a.coords[3 * v + 2]; return; }
-    v += a.v_offset;
-    const long long k = v % a.gn[2], j = (v / a.gn[2]) % a.gn[1], i = v / ((long long) a.gn[2] * a.gn[1]);
-    x[0] = a.glo[0] + a.gstep[0] * (float) i;
-    x[1] = a.glo[1] + a.gstep[1] * (float) j;
-    x[2] = a.glo[2] + a.gstep[2] * (float) k;
-}
-}  // namespace bw
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // data path: 64 voxels per 512-thread block, the tiling and the k-step of k_mlp_forward_x3 (A = transposed-weight fragments in
@@ -81,7 +40,6 @@ __device__ __forceinline__ void voxel_xyz(const MlpArgs &a, long long v, float x
 // ---------------------------------------------------------------------------------------------------------------------------
 template <bool FULL>                // FULL: hidden width 512 (see k_mlp_forward_x3)
 __global__ void __launch_bounds__(512) k_mlp_backward_x3(MlpBwdArgs a) {
-    using namespace bw;
     extern __shared__ __align__(16) unsigned char smem[];
     _Float16 *Hh = reinterpret_cast<_Float16 *>(smem);
     _Float16 *Hl = Hh + TM * HS;
@@ -126,7 +84,7 @@ __global__ void __launch_bounds__(512) k_mlp_backward_x3(MlpBwdArgs a) {
                     if (!pos) continue;
                     if (is_top) {
                         _Float16 xh, xl;
-                        split_scaled(g * a.wout[8 * c + j], xh, xl);
+                        split(g * a.wout[8 * c + j], xh, xl);
                         oh[j] = xh; ol[j] = xl;
                     } else { oh[j] = rh[j]; ol[j] = rl[j]; }
                     ou[j] = (_Float16) ((float) ol[j] * LO_INV);
@@ -207,7 +165,7 @@ __global__ void __launch_bounds__(512) k_mlp_backward_x3(MlpBwdArgs a) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         _Float16 yh, yl;
-                        split_scaled(fmaf(accx[t][c][4 * g + q], LO_INV, acch[t][c][4 * g + q]), yh, yl);
+                        split(fmaf(accx[t][c][4 * g + q], LO_INV, acch[t][c][4 * g + q]), yh, yl);
                         oh[q] = yh; ol[q] = yl;
                     }
                     *reinterpret_cast<h4_t *>(Hh + (c * 32 + r) * HS + n) = oh;
@@ -221,7 +179,6 @@ __global__ void __launch_bounds__(512) k_mlp_backward_x3(MlpBwdArgs a) {
 }
 
 void launch_mlp_backward_x3(const MlpBwdArgs &a, long long rows, hipStream_t s) {
-    using namespace bw;
     if (a.nn % 32 || a.nn > MAXN) throw Error("MLP backward: hidden width must be a multiple of 32 up to 512");
     if (rows % TM) throw Error("MLP backward: the padded chunk must be a multiple of 64 voxels");
     const size_t lds = (size_t) 2 * TM * HS * 2 + TM * sizeof(float);
@@ -265,7 +222,6 @@ using First = Shape<256, 256, 32>;      // (Shape<512, 128, 16>: measured slower
 
 template <int TERMS, bool FEATURES, class C>
 __global__ void __launch_bounds__(512) k_mlp_dw(MlpDwArgs a) {
-    using namespace bw;
     constexpr int BN = C::BN, BK = C::BK, SV = C::SV, PA = C::PA, PB = C::PB, IA = C::IA, IB = C::IB, STAGE = C::STAGE;
     extern __shared__ __align__(16) unsigned char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -521,7 +477,6 @@ void launch_mlp_dw(const MlpDwArgs &a, hipStream_t s) {
 // 256 threads: a thread owns eight consecutive columns (16-byte loads) and every (256 / (ncols / 8))-th row of the block's rows
 __global__ void __launch_bounds__(256) k_colsum_split(long long rows, int ncols, const _Float16 *__restrict__ Xh, const _Float16 *__restrict__ Xl,
                                                       const float *__restrict__ w, float *__restrict__ partial) {
-    using namespace bw;
     __shared__ float red[256 * 8];
     const int groups = ncols / 8;                       // column groups (<= 64)
     const int lanes = 256 / groups;                     // row lanes per group

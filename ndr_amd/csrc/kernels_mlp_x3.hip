@@ -23,71 +23,16 @@
 #include <hip/hip_fp16.h>
 
 #include "mlp_args.h"
+#include "mlp_device.h"
 
 namespace vfem {
 
-namespace x3 {
-typedef _Float16 h8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
-typedef float f16_t __attribute__((ext_vector_type(16)));
-constexpr int TM = 64;                    // voxels per block
-constexpr int MAXN = 512;                 // hidden width limit
-constexpr int HS = MAXN + 8;              // halves per activation row (16-byte pad: conflict-free ds_read_b128)
-// feature chunk of the first layer: KC columns = the sines of KC / 2 rows of B followed by their cosines (one barrier per chunk: 128
-// where the embedding size allows it -- a multiple of 64 --, else 64); FS = KC + 8 halves per staged feature row
-constexpr float LO_SCALE = 2048.f, LO_INV = 1.f / 2048.f;
-
-__device__ __forceinline__ void split(float x, _Float16 &hi, _Float16 &lo) {
-    hi = (_Float16) x;
-    lo = (_Float16) ((x - (float) hi) * LO_SCALE);
-}
-// sin and cos of an fp32 argument together, to fp32 rounding (max error 9.2e-8 for |t| <= 1000, tools/ numpy check in DESIGN 3.5; numpy's own
-// fp32 sin: 7e-8): one Cody-Waite reduction by pi/2 in three fma steps (pi/2 = c1 + c2 + c3), the cephes single-precision minimax
-// polynomials on [-pi/4, pi/4], quadrant by the low bits of n.  ~25 instructions for the pair; two library calls (sinf, cosf) were ~90
-// and made feature generation 27 % of the SIMD time of the forward kernel (profiles/r04_mlp_x3_pmc.json: 1686 vector instructions per voxel).
-__device__ __forceinline__ void sincos_f32(float t, float &sn, float &cs) {
-    const float n = __builtin_rintf(t * 0.636619772367581343f);
-    float y = fmaf(-n, 1.5707963705062866f, t);
-    y = fmaf(-n, -4.371138828673793e-08f, y);
-    y = fmaf(-n, -1.7763568394002505e-15f, y);
-    const float z = y * y;
-    float ps = fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f);
-    ps = fmaf(ps, z, -1.6666654611e-1f);
-    const float s = fmaf(ps * z, y, y);
-    float pc = fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f);
-    pc = fmaf(pc, z, 4.166664568298827e-2f);
-    const float c = fmaf(z * z, pc, fmaf(-0.5f, z, 1.0f));
-    const int q = (int) n;
-    const float a = (q & 1) ? c : s, b = (q & 1) ? s : c;
-    sn = (q & 2) ? -a : a;
-    cs = ((q + 1) & 2) ? -b : b;
-}
-__device__ __forceinline__ void voxel_xyz(const MlpArgs &a, long long v, float x[3]) {
-    if (a.coords) { x[0] = a.coords[3 * v]; x[1] = a.coords[3 * v + 1]; x[2] = a.coords[3 * v + 2]; return; }
-    v += a.v_offset;
-    const long long k = v % a.gn[2], j = (v / a.gn[2]) % a.gn[1], i = v / ((long long) a.gn[2] * a.gn[1]);
-    x[0] = a.glo[0] + a.gstep[0] * (float) i;
-    x[1] = a.glo[1] + a.gstep[1] * (float) j;
-    x[2] = a.glo[2] + a.gstep[2] * (float) k;
-}
-// the low half without its 2^11 scale (what the backward pass's products take).  A nonzero half never becomes zero: an activation
-// of 1e-9 has hi = 0 and lives in its low half alone, whose unscaled value underflows fp16 -- and "h > 0" is the ReLU mask of the
-// backward pass (the smallest subnormal, 6e-8, stands in: its value is immaterial, its sign is not)
-__device__ __forceinline__ _Float16 unscale_lo(_Float16 ls) {
-    const float f = (float) ls;
-    _Float16 u = (_Float16) (f * LO_INV);
-    if ((float) u == 0.f && f != 0.f) u = (_Float16) (f > 0.f ? 5.9604645e-8f : -5.9604645e-8f);
-    return u;
-}
-}  // namespace x3
+using namespace mlp;
 
 struct MlpX3Weights { const _Float16 *W1h, *W1l, *Whh, *Whl; };
 
-// weights: hi / lo halves of an fp32 array
-__global__ void __launch_bounds__(256) k_split_f32(long long n, const float *__restrict__ in, _Float16 *__restrict__ hi, _Float16 *__restrict__ lo) {
-    for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long) gridDim.x * blockDim.x) x3::split(in[i], hi[i], lo[i]);
-}
-// The same halves in MFMA-FRAGMENT order: the A operand of v_mfma_f32_32x32x16_f16 for the row tile T (32 rows) and k-step S is, per
+// weights: the hi / lo halves of an fp32 array, in MFMA-FRAGMENT order.
+// The A operand of v_mfma_f32_32x32x16_f16 for the row tile T (32 rows) and k-step S is, per
 // lane (r = lane & 31, h = lane >> 5), the eight halves W[32 T + r][16 S + 8 h .. + 7].  Row-major, the 64 lanes of that load touch 32
 // rows = 32 separate 32-byte pieces: the forward kernel then sits on the L2's REQUEST rate (profiles/r04_mlp_x3_pmc.json: 99 % L2 hits,
 // 0.74 requests per clock and channel, waves 63 % of their time in s_waitcnt).  Stored as [T][S][lane][8] the load is one contiguous KB
@@ -103,7 +48,7 @@ __global__ void __launch_bounds__(256) k_split_f32_frag(int N, int K, int pair_e
         int k = (int) (i - (long long) row * K);
         if (pair_es > 0) { const int f = k < pair_es ? k : k - pair_es; k = pair_kc * (f / (pair_kc / 2)) + f % (pair_kc / 2) + (k < pair_es ? 0 : pair_kc / 2); }
         const long long o = ((((long long) (row >> 5) * nks + (k >> 4)) * 64) + (row & 31) + 32 * ((k >> 3) & 1)) * 8 + (k & 7);
-        x3::split(transposed ? in[(long long) (int) (i - (long long) row * K) * N + row] : in[i], hi[o], lo[o]);
+        split(transposed ? in[(long long) (int) (i - (long long) row * K) * N + row] : in[i], hi[o], lo[o]);
     }
 }
 void launch_split_f32_frag(int N, int K, const float *in, void *hi, void *lo, hipStream_t s, int pair_es, int transposed, int pair_kc) {
@@ -127,16 +72,12 @@ void launch_range_check_f32(long long n, const float *in, float limit, int *flag
     k_range_check_f32<<<dim3((unsigned) g), 256, 0, s>>>(n, in, limit, flag);
     VFEM_HIP(hipGetLastError());
 }
-void launch_split_f32(long long n, const float *in, void *hi, void *lo, hipStream_t s) {
-    long long g = (n + 255) / 256;
-    if (g > 4096) g = 4096;
-    k_split_f32<<<dim3((unsigned) (g < 1 ? 1 : g)), 256, 0, s>>>(n, in, (_Float16 *) hi, (_Float16 *) lo);
-    VFEM_HIP(hipGetLastError());
-}
 
-template <bool FULL, int KC>        // FULL: hidden width 512 = 16 row tiles, both tiles of every wave live: the branches on tile validity fold away
+// FULL: hidden width 512 = 16 row tiles, both tiles of every wave live: the branches on tile validity fold away
+// KC: feature chunk of the first layer: KC columns = the sines of KC / 2 rows of B followed by their cosines (one barrier per chunk: 128
+// where the embedding size allows it -- a multiple of 64 --, else 64); FS = KC + 8 halves per staged feature row
+template <bool FULL, int KC>
 __global__ void __launch_bounds__(512) k_mlp_forward_x3(MlpArgs a, MlpX3Weights w) {
-    using namespace x3;
     constexpr int FS = KC + 8;
     extern __shared__ __align__(16) unsigned char smem[];
     _Float16 *Hh = reinterpret_cast<_Float16 *>(smem);                       // [64][HS] high halves of the activations
@@ -390,7 +331,6 @@ __global__ void __launch_bounds__(512) k_mlp_forward_x3(MlpArgs a, MlpX3Weights 
 }
 
 void launch_mlp_forward_x3(const MlpArgs &a, const void *W1h, const void *W1l, const void *Whh, const void *Whl, hipStream_t s, int kc) {
-    using namespace x3;
     if (a.nn % 32 || a.nn > MAXN || a.es % 32) throw Error("fused MLP kernel: hidden width must be a multiple of 32 up to 512, embedding size a multiple of 32");
     if ((kc != 64 && kc != 128) || a.es % (kc / 2)) throw Error("fused MLP kernel: feature chunk 64 or 128, embedding size a multiple of half of it");
     const size_t lds = (size_t) 2 * TM * HS * 2 + TM * 3 * sizeof(float);

@@ -388,7 +388,6 @@ constexpr int Q2M_OB = 448;                                   // doubles per par
 
 typedef unsigned int q2u4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int q2u2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ double q2_mkd(unsigned lo, unsigned hi) { return __longlong_as_double(((unsigned long long) hi << 32) | lo); }
 
 // Round 4: rows reach and leave the lanes DIRECTLY.  Rounds 1-3 loaded a row segment in lane-contiguous pieces and turned it into the
 // 9 values (3 nodes x 3 components) of every lane's element through LDS (7 writes + 9 reads and two wave barriers per row, twelve
@@ -436,10 +435,10 @@ __global__ void __launch_bounds__(256) k_apply_q2_march(DimsQ2 d, const double *
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const q2u4_t w = __builtin_amdgcn_raw_buffer_load_b128(r, eoff + 16 * q, 0, 0);
-            dst[2 * q] = q2_mkd(w.x, w.y); dst[2 * q + 1] = q2_mkd(w.z, w.w);
+            dst[2 * q] = mkd(w.x, w.y); dst[2 * q + 1] = mkd(w.z, w.w);
         }
         const q2u2_t w = __builtin_amdgcn_raw_buffer_load_b64(r, eoff + 64, 0, 0);
-        dst[8] = q2_mkd(w.x, w.y);
+        dst[8] = mkd(w.x, w.y);
     };
     auto issue_loads = [&](int ex) {
         if (EXP == 3) { Enext = E[((long long) ex * d.ny + eyc) * d.nz + ezc]; return; }

@@ -245,7 +245,6 @@ void band_direct_solve(BandSolver &bs, long long version, int N, int p, const in
 
 struct MlpArgs;
 void launch_mlp_forward(const MlpArgs &a, hipStream_t s);
-void launch_f32_to_f16(long long n, const float *in, void *out, hipStream_t s);
 struct MlpBwdArgs;
 struct MlpDwArgs;
 void launch_mlp_backward_x3(const MlpBwdArgs &a, long long rows, hipStream_t s);
@@ -256,7 +255,6 @@ void launch_f32_to_f16_frag(int N, int K, int transposed, const float *in, void 
 void launch_range_check_f32(long long n, const float *in, float limit, int *flag, hipStream_t s);
 void launch_split_f32_frag(int N, int K, const float *in, void *hi, void *lo, hipStream_t s, int pair_es, int transposed = 0, int pair_kc = 64);
 void launch_mlp_forward_x3(const MlpArgs &a, const void *W1h, const void *W1l, const void *Whh, const void *Whl, hipStream_t s, int kc);
-void launch_split_f32(long long n, const float *in, void *hi, void *lo, hipStream_t s);
 void launch_reduce_partials(int nb, long long n, const float *partial, float alpha, float beta, float *out, hipStream_t s);
 void launch_sum_f32(long long n, const float *x, float alpha, float beta, float *out, float *scratch, hipStream_t s);
 void launch_adam(long long n, float *p, const float *g, float *m, float *v, float lr, float b1, float b2, float eps, int step, hipStream_t s);

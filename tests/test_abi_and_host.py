@@ -96,6 +96,17 @@ def test_product_never_imports_oracle():
                 assert "import oracle" not in txt and "from oracle" not in txt and "voxel_ref" not in txt, (dirpath, f)
 
 
+@pytest.mark.parametrize("name", ["sincos_f32", "voxel_xyz", "unscale_lo", "mkd", "glds16"])
+def test_shared_device_helpers_are_defined_once(name):
+    """the backward MLP kernels must see the forward kernels' features, coordinates and ReLU masks bit for bit (mlp_device.h), and
+    mkd / glds16 live in device_utils.h: a second definition in any kernel file is a copy that can drift"""
+    csrc = os.path.join(ROOT, "ndr_amd", "csrc")
+    definition = re.compile(r"^[ \t]*__device__\b[^;{}()]*\b%s[ \t]*\(" % name, re.M)
+    found = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))
+             for _ in definition.finditer(open(os.path.join(csrc, f)).read())]
+    assert found == ["device_utils.h" if name in ("mkd", "glds16") else "mlp_device.h"]
+
+
 @pytest.mark.gpu
 def test_filters_and_constraint_match_oracle():
     from ndr_amd import pyVoxelFEM as pv
