@@ -194,6 +194,19 @@ int vfem_mg_zero_dirichlet(vfem_mg *mg, int level, double *u, void *stream);
 int vfem_mg_restrict(vfem_mg *mg, int fine_level, const double *fine, double *coarse, void *stream);
 int vfem_mg_interpolate(vfem_mg *mg, int fine_level, const double *coarse, double *fine, int accumulate, void *stream);
 int vfem_mg_coarsest_solve(vfem_mg *mg, const double *b, double *x, void *stream);
+/* How the coarsest level is solved exactly (the reference: CHOLMOD, TPS.hh:834-865, at any size).
+ *   VFEM_COARSEST_DENSE   the dense n x n inverse applied as a GEMV; refuses more than 40 000 dofs.
+ *   VFEM_COARSEST_PLANES  block tridiagonal Cholesky over the x planes (plane_spd.hip): one dense inverse T_j of m = 3 NY NZ dofs per
+ *                         node plane, NX m^2 doubles, the solve a forward and a backward march over the planes (about 4 NX launches,
+ *                         stream-ordered).  Refuses when the blocks and the factorisation's workspace exceed 8 GiB.
+ *   VFEM_COARSEST_AUTO    (default) dense up to 40 000 dofs, plane blocks above.
+ * Both treat a fixed dof alike (x = 0 there, b ignored) and agree to rounding (different elimination orders).  Changing the mode
+ * discards the kept factorisation; the next solve or vfem_mg_update_operators builds the other one.  An unknown mode is an error.
+ * vfem_mg_coarsest_bytes: device bytes the kept factorisation holds (the dense inverse, or the plane blocks with the solver's
+ * copy of the coupling entries); 0 while none is kept. */
+enum { VFEM_COARSEST_AUTO = 0, VFEM_COARSEST_DENSE = 1, VFEM_COARSEST_PLANES = 2 };
+int vfem_mg_set_coarsest_solver(vfem_mg *mg, int mode);
+int64_t vfem_mg_coarsest_bytes(const vfem_mg *mg);
 /* The factorisation behind the exact coarsest solve (TPS::solve with CholmodFactorizer, TPS.hh:834-865, SparseMatrices.hh:1875-1965),
  * as this library does it: A (n x n doubles, row-major, symmetric positive definite, both triangles) is replaced in place by
  * its inverse (both triangles).  Own blocked Cholesky / triangular inverse / product kernels on `stream`, fixed summation

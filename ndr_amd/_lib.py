@@ -84,6 +84,8 @@ SIGNATURES = {
     "vfem_mg_restrict": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "vfem_mg_interpolate": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "vfem_mg_coarsest_solve": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vfem_mg_set_coarsest_solver": (c_int, [c_void_p, c_int]),
+    "vfem_mg_coarsest_bytes": (c_int64, [c_void_p]),
     "vfem_dense_spd_inverse": (c_int, [c_int64, c_void_p, c_void_p]),
     "vfem_band_spd_factor": (c_int, [c_int64, c_int64, c_void_p, c_void_p]),
     "vfem_band_spd_solve": (c_int, [c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),

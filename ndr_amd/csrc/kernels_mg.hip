@@ -1530,6 +1530,41 @@ void launch_dense_from_stencil(const Dims &d, const double *S, const uint8_t *ma
     VFEM_HIP(hipGetLastError());
 }
 
+// the same matrix for the plane-block coarsest solver (plane_spd.hip): node-major copy of its rows, R[n][nb][3 r + c] with
+// 243 doubles per node, fixed rows/columns replaced by identity and neighbours outside the grid by zero.  The copy owns its
+// values: nothing of the colour-major stencil is read after this launch.
+__global__ void __launch_bounds__(256) k_plane_rows_from_stencil(Dims d, const double *__restrict__ St,
+                                                                 const uint8_t *__restrict__ mask, double *__restrict__ R) {
+    const long long gid = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= d.nn * 27) return;
+    const long long n = gid / 27;
+    const int nb = (int) (gid - n * 27);
+    const int k = (int) (n % d.NZ), j = (int) ((n / d.NZ) % d.NY), i = (int) (n / ((long long) d.NZ * d.NY));
+    const int ii = i + nb / 9 - 1, jj = j + (nb / 3) % 3 - 1, kk = k + nb % 3 - 1;
+    double *out = R + gid * 9;
+    if (ii < 0 || ii >= d.NX || jj < 0 || jj >= d.NY || kk < 0 || kk >= d.NZ) {
+        for (int q = 0; q < 9; ++q) out[q] = 0.0;
+        return;
+    }
+    const long long m = nidx(d, ii, jj, kk);
+    long long sbase, scnt;
+    cm_index(d, i, j, k, sbase, scnt);
+    const uint8_t mn = mask[n], mm = mask[m];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            double v = St[sbase + ((long long) nb * 9 + 3 * r + c) * scnt];
+            const bool fr = (mn >> r) & 1, fc = (mm >> c) & 1;
+            if (fr || fc) v = (n == m && r == c) ? 1.0 : 0.0;
+            out[3 * r + c] = v;
+        }
+}
+
+void launch_plane_rows_from_stencil(const Dims &d, const double *S, const uint8_t *mask, double *R, hipStream_t s) {
+    const long long total = d.nn * 27;
+    k_plane_rows_from_stencil<<<dim3((unsigned) ((total + 255) / 256)), dim3(256), 0, s>>>(d, S, mask, R);
+    VFEM_HIP(hipGetLastError());
+}
+
 // after potrf+potri(lower, column-major == upper, row-major): mirror the computed triangle and zero the
 // rows/columns of fixed dofs so that x_fixed = 0 and rhs_fixed is ignored.
 __global__ void __launch_bounds__(256) k_dense_finish(long long n, const uint8_t *__restrict__ mask, double *__restrict__ A) {

@@ -203,6 +203,7 @@ bool vfem::mg_smooth_half(vfem_mg *mg, int l, double *u, const double *b, int fo
 }
 
 static void coarsest_solve(vfem_mg *mg, const double *b, double *x, hipStream_t s) {
+    if (mg->coarsest_planes) { plane_spd_solve(mg->planes, b, x, s); return; }
     const long long n = 3 * mg->lv[mg->L].d.nn;
     launch_gemv_sym(n, mg->Ainv.p, b, x, s);
 }
@@ -253,11 +254,14 @@ void vfem::update_operators(vfem_mg *mg, hipStream_t s) {
         } else lv.Sn.release();
     }
     if (mg->slab) { mg->operators_valid = true; mg->operators_version = sim->operator_version; return; }       // the coarse levels live in the replicated hierarchy
-    // coarsest level: dense inverse
+    // coarsest level: dense inverse, or the plane-block factorisation (plane_spd.hip) where the mode asks for it -- auto: above the
+    // dense path's limit.  Both refuse before anything is allocated
     MgLevel &cl = mg->lv[L];
     const long long n = 3 * cl.d.nn;
-    if (n > 40000) throw Error("coarsest grid too large for the dense coarsest-level solve (" + std::to_string(n) +
-                               " dofs); use more coarsening levels");
+    const bool planes = mg->coarsest_mode == VFEM_COARSEST_PLANES || (mg->coarsest_mode == VFEM_COARSEST_AUTO && n > 40000);
+    if (planes ? plane_spd_bytes_needed(cl.d) > PLANE_SPD_MAX_BYTES : n > 40000)
+        throw Error("coarsest grid too large for the " + std::string(planes ? "plane-block" : "dense") + " coarsest-level solve (" +
+                    std::to_string(n) + " dofs); use more coarsening levels");
     const double *Sc = cl.S.p;
     DevBuf<double> tmpS;
     if (L < 2) {
@@ -265,6 +269,17 @@ void vfem::update_operators(vfem_mg *mg, hipStream_t s) {
         launch_stencil_from_mf(cl.d, L == 0 ? OP_MF0 : OP_MF1, level_K(mg, L), level_E(mg, L), tmpS.p, s);
         Sc = tmpS.p;
     }
+    if (planes) {
+        mg->Ainv.release();
+        plane_spd_factor(mg->planes, cl.d, Sc, cl.maskp, mg->dense, s);
+        VFEM_HIP(hipStreamSynchronize(s));   // tmpS lifetime
+        mg->coarsest_planes = true;
+        mg->operators_valid = true;
+        mg->operators_version = sim->operator_version;
+        return;
+    }
+    mg->planes.release();
+    mg->coarsest_planes = false;
     mg->Ainv.alloc((size_t) n * n);
     mg->Ainv.zero(s);
     launch_dense_from_stencil(cl.d, Sc, cl.maskp, mg->Ainv.p, s);
@@ -576,6 +591,18 @@ int vfem_mg_coarsest_solve(vfem_mg *mg, const double *b, double *x, void *stream
     update_operators(mg, S(stream));
     coarsest_solve(mg, b, x, S(stream));
     VFEM_CATCH
+}
+int vfem_mg_set_coarsest_solver(vfem_mg *mg, int mode) {
+    VFEM_TRY
+    if (mode != VFEM_COARSEST_AUTO && mode != VFEM_COARSEST_DENSE && mode != VFEM_COARSEST_PLANES)
+        throw Error("unknown coarsest-level solver mode " + std::to_string(mode));
+    if (mode != mg->coarsest_mode) mg->operators_valid = false;      // the kept factorisation belongs to the old mode
+    mg->coarsest_mode = mode;
+    VFEM_CATCH
+}
+int64_t vfem_mg_coarsest_bytes(const vfem_mg *mg) {
+    if (!mg->operators_valid || mg->slab) return 0;
+    return mg->coarsest_planes ? mg->planes.bytes() : (int64_t) (mg->Ainv.n * sizeof(double));
 }
 
 int vfem_mg_smooth_colors(vfem_mg *mg, int level, double *u, const double *b, int forward, int first, int count, void *stream) {

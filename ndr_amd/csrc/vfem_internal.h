@@ -176,6 +176,8 @@ void launch_stencil_from_ke(const Dims &d, const double *Ke, double *S, hipStrea
 void launch_stencil_from_mf(const Dims &d, OpKind kind, const double *K, const double *E, double *S, hipStream_t s);
 void launch_dense_from_stencil(const Dims &d, const double *S, const uint8_t *mask, double *A, hipStream_t s);
 void launch_dense_finish_inverse(long long n, const uint8_t *mask, double *A, hipStream_t s);
+// node-major rows of the same matrix (fixed rows / columns replaced by identity), [nn][27][9]: what plane_spd.hip keeps
+void launch_plane_rows_from_stencil(const Dims &d, const double *S, const uint8_t *mask, double *R, hipStream_t s);
 void launch_gemv_sym(long long n, const double *A, const double *x, double *y, hipStream_t s);
 
 void launch_compliance_gradient(const Dims &d, const double *K0, const double *rho, double E0, double Emin,
@@ -214,6 +216,24 @@ void launch_gs_sweep_q2_level0(int nx, int ny, int nz, const double *K0, const d
 // bitwise reproducible whatever else shares the device.  Throws when a pivot is not positive.  The workspace grows, never shrinks.
 struct DenseWork { DevBuf<double> L, X, Tm, D; DevBuf<int> info; };
 void dense_spd_inverse(long long n, double *A, DenseWork &w, hipStream_t s);
+// Plane-block tridiagonal Cholesky of the coarsest level (plane_spd.hip): K in blocks over the x planes (m = 3 NY NZ dofs each),
+// T_j = (A_j - C_j T_{j-1} C_j^T)^-1 kept dense per plane, the solve a forward and a backward march over the planes.  The solver
+// owns its storage; the stencil it is built from may be released after plane_spd_factor returns.
+struct PlaneSolver {
+    Dims d;
+    DevBuf<double> T;               // NX blocks of m x m, row-major: the inverted Schur complements, fixed rows / columns zero
+    DevBuf<double> R;               // [nn][27][9]: node-major rows of K, fixed rows / columns replaced by identity
+    DevBuf<double> W;               // m x m: T_{j-1} C_j^T while plane j is factorised
+    DevBuf<double> z, t;            // solve: n and m doubles
+    long long m() const { return 3LL * d.NY * d.NZ; }
+    long long bytes() const { return (long long) ((T.n + R.n) * sizeof(double)); }
+    void release() { T.release(); R.release(); W.release(); z.release(); t.release(); }
+};
+constexpr long long PLANE_SPD_MAX_BYTES = 8LL << 30;      // the cap of the band solver (band.py BAND_CAP_BYTES): blocks + factorisation workspace
+long long plane_spd_bytes_needed(const Dims &d);           // T, R, W, the vectors and dense_spd_inverse's workspace at size m
+// S: the level's colour-major stencil.  Synchronises s (once per plane: the pivot check of dense_spd_inverse)
+void plane_spd_factor(PlaneSolver &ps, const Dims &d, const double *S, const uint8_t *mask, DenseWork &w, hipStream_t s);
+void plane_spd_solve(PlaneSolver &ps, const double *b, double *x, hipStream_t s);        // stream-ordered, 4 NX - 3 launches
 void launch_gs_sweep_q2_level1(int nx, int ny, int nz, const double *cK0, const double *Ef, int fx0, double *u, const double *b,
                                const uint8_t *mask, int forward, hipStream_t s, int first = 0, int count = 27);
 void launch_apply_q2_level1(int nx, int ny, int nz, const double *cK0, const double *Ef, int fx0, const double *u, const double *b,
@@ -329,6 +349,9 @@ struct vfem_mg {
     long long operators_version = 0;            // fine->operator_version the coarse operators were built for
     bool mf1_sym = false;                       // cK0[f] are mirror images of cK0[0]: level-1 sweeps read cK0[0] only
     vfem::DenseWork dense;                      // workspace of the coarsest-level inverse
+    int coarsest_mode = 0;                      // VFEM_COARSEST_AUTO / _DENSE / _PLANES (vfem_mg_set_coarsest_solver)
+    bool coarsest_planes = false;               // the factorisation held is the plane-block one (planes), not Ainv
+    vfem::PlaneSolver planes;                   // coarsest-level plane-block factorisation (plane_spd.hip)
 };
 
 struct vfem_mlp {

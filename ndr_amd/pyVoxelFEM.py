@@ -425,6 +425,30 @@ class MultigridSolver1_1_1(_MultigridSolver):
     solve and its work vectors."""
 
     _MG_PREFIX = "vfem_mg_"
+    _COARSEST_MODES = {"auto": 0, "dense": 1, "planes": 2}          # VFEM_COARSEST_* of include/vfem.h
+
+    # coarsestSolver and coarsestBytes are attributes of the instances, like last_iterations: the public names of the class itself
+    # are those of the reference's binding plus the three debug entries.
+    #   mg.coarsestSolver = "auto" | "dense" | "planes"   how the coarsest level is solved: "dense" (n x n inverse, at most 40 000
+    #       dofs), "planes" (block tridiagonal Cholesky over the x planes, any size that fits 8 GiB) or "auto" (the default: dense up
+    #       to its limit, plane blocks above).  Assigning another mode discards the kept factorisation; an unknown one raises.
+    #   mg.coarsestBytes()   device bytes of the coarsest-level factorisation currently kept (0 before the first operator update)
+    def __setattr__(self, name, value):
+        if name == "coarsestSolver":
+            if value not in self._COARSEST_MODES:
+                raise RuntimeError("coarsestSolver must be one of %s, not %r" % (sorted(self._COARSEST_MODES), value))
+            _lib.check(self._mg("set_coarsest_solver")(self._h, self._COARSEST_MODES[value]))
+        object.__setattr__(self, name, value)
+
+    def __getattr__(self, name):          # (only reached for names that are neither set on the instance nor defined by the class)
+        if name == "coarsestSolver":
+            return "auto"
+        if name == "coarsestBytes":
+            return self._coarsest_bytes
+        raise AttributeError(name)
+
+    def _coarsest_bytes(self):
+        return int(self._mg("coarsest_bytes")(self._h))
 
     def coarsestSolve_device(self, b):
         b = _to_dev(b, (self._nn(self.L), 3))
