@@ -70,7 +70,7 @@ int vfem_stream_sync(void *stream) { VFEM_TRY VFEM_HIP(hipStreamSynchronize(S(st
 
 int vfem_dense_spd_inverse(int64_t n, double *A, void *stream) {
     VFEM_TRY
-    if (n < 1 || n > 40000) throw Error("dense inverse: n must be in [1, 40000]");      // (n = 40 000: 12.8 GB + three work matrices of the padded size = 51 GB)
+    if (n < 1 || n > DENSE_COARSEST_MAX_DOFS) throw Error("dense inverse: n must be in [1, " + std::to_string(DENSE_COARSEST_MAX_DOFS) + "]");
     DenseWork w;
     dense_spd_inverse(n, A, w, S(stream));
     VFEM_HIP(hipStreamSynchronize(S(stream)));      // the workspace is released on return

@@ -12,7 +12,7 @@
 #include "mg_cycle.h"
 #include "device_utils.h"
 #include "q2_modes.h"
-
+#include "gs_colors.h"
 
 #include <algorithm>
 #include <cmath>
@@ -238,7 +238,7 @@ __global__ void __launch_bounds__(256) kg_apply(GDims d, const double *__restric
     }
 }
 
-struct GColor { int start[3], inc[3], cnt[3]; long long total; };
+struct GColor : GsColor { long long total; };      // ... and how many nodes: one wave each
 
 // component-sequential solve of m_smoothNode (MG.hh:254-264) for the node the wave gathered
 __device__ __forceinline__ void g_relax(const GDims &d, int N, long long n, const double S[3], const double M[9], double *__restrict__ u,
@@ -282,20 +282,7 @@ __global__ void __launch_bounds__(256) kg_gs_color(GDims d, GColor col, const do
     { long long m = w; for (int a = N - 1; a >= 0; --a) { idx[a] = col.start[a] + (int) (m % col.cnt[a]) * col.inc[a]; m /= col.cnt[a]; } }
     double S[3], M[9];
     g_gather<N, p>(d, K, kstride, scale, u, idx, lane, S, M);
-    if (lane == 0) {
-        const long long n = g_node_flat_n<N>(d, idx);
-        const uint8_t dc = mask ? mask[n] : 0;
-        double bms[3], diff[3] = {0.0, 0.0, 0.0};
-        for (int r = 0; r < N; ++r) bms[r] = b[N * n + r] - S[r];
-        for (int s = 0; s < N; ++s) {
-            const int i = forward ? s : N - 1 - s;
-            double acc = 0.0;
-            for (int c = 0; c < N; ++c) acc += M[3 * i + c] * diff[c];
-            const double fac = (double) (((dc >> i) & 1) == 0) / M[3 * i + i];
-            diff[i] = (bms[i] - acc) * fac;
-        }
-        for (int r = 0; r < N; ++r) u[N * n + r] += diff[r];
-    }
+    if (lane == 0) g_relax(d, N, g_node_flat_n<N>(d, idx), S, M, u, b, mask, forward);
 }
 
 __device__ __forceinline__ long long g_child(const GDims &f, const GDims &c, long long ec, int fi);
@@ -589,15 +576,6 @@ __global__ void kg_dirichlet(long long nn, int N, const uint8_t *__restrict__ ma
     if ((mask[i / N] >> (i % N)) & 1) u[i] = vals ? vals[i] : 0.0;
 }
 
-__global__ void kg_dense_finish(long long n, int N, const uint8_t *__restrict__ mask, double *__restrict__ A) {
-    const long long gid = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= n * n) return;
-    const long long r = gid / n, c = gid % n;
-    const bool fr = (mask[r / N] >> (r % N)) & 1, fc = (mask[c / N] >> (c % N)) & 1;
-    if (fr || fc) { A[gid] = 0.0; return; }
-    if (c < r) A[gid] = A[c * n + r];      // rocSOLVER "lower" (column-major) = row-major upper triangle
-}
-
 __global__ void __launch_bounds__(256) kg_gradient(GDims d, const double *__restrict__ K0, const double *__restrict__ rho,
                                                    double E0, double Emin, double gamma, const double *__restrict__ u,
                                                    double *__restrict__ g) {
@@ -687,11 +665,11 @@ struct vfem_gmg {
     bool l1_virtual = false;           // degree 2: level 1 applies sum_f E_f cK0[f] on the fly, lv[1].Ke is not stored
     std::vector<GLevel> lv;
     GWeights W;
-    DevBuf<double> cK0, phi, Ainv, pd, pAd, ps, scal, scratch;
+    DevBuf<double> cK0, phi, pd, pAd, ps, scal, scratch;
     DevBuf<double> tr1, tr2;           // intermediates of the axis-by-axis transfers
     DevBuf<double> c2tab;              // degree-2 hexahedra: c2K0[g][f] = I_g^T cK0[f] I_g as [entry][64] (level 2 straight from the moduli)
     DevBuf<double> l1tab;              // degree-2 hexahedra: cK0 regrouped for k_q2_level1, [ln][m][f][r][c]
-    vfem::DenseWork dense;             // workspace of the coarsest-level inverse (dense_spd.hip)
+    CoarsestSolver coarsest;           // exact solve of level L: always the dense inverse here (mode auto = dense)
 };
 
 static double lagrange1d(int p, int a, double x) {            // LagrangePolynomial.hh:9,42-56
@@ -851,45 +829,18 @@ static void gmg_smooth(vfem_gmg *mg, int l, double *u, const double *b, int forw
     }
     const double *K, *scale; long long ks;
     level_op(mg, l, K, ks, scale);
-    int ncol = 1;
-    for (int a = 0; a < d.N; ++a) ncol *= d.p + 1;
-    for (int i = first; i < std::min(ncol, first + count); ++i) {
-        const int lni = forward ? i : ncol - 1 - i;                   // MG.hh:293-295
-        GColor col{};
-        col.total = 1;
-        int m = lni;
-        for (int a = d.N - 1; a >= 0; --a) {
-            const int la = m % (d.p + 1); m /= d.p + 1;
-            const bool boundary = la == 0 || la == d.p;
-            col.start[a] = la;
-            col.inc[a] = (1 + (boundary ? 1 : 0)) * d.p;              // MG.hh:301-305
-            col.cnt[a] = la > d.nn[a] - 1 ? 0 : (d.nn[a] - 1 - la) / col.inc[a] + 1;
-            col.total *= col.cnt[a];
-        }
-        for (int a = d.N; a < 3; ++a) { col.start[a] = 0; col.inc[a] = 1; col.cnt[a] = 1; }
-        if (col.total == 0) continue;
+    const uint8_t *mk = mg->lv[l].mask.p;
+    for_each_gs_color(d.N, d.p, d.nn, forward, first, count, [&](const GsColor &gc) {
+        const GColor col{gc, (long long) gc.cnt[0] * gc.cnt[1] * gc.cnt[2]};
         const dim3 grd((unsigned) ((col.total + 3) / 4)), blk(256);
-        const uint8_t *mk = mg->lv[l].mask.p;
-        if (d.N == 3 && d.p == 2) {
-            // incident elements per axis: 1 for a mid node (local index 1), 2 for a node on an element boundary
-#define VFEM_GSF(A, B, C) kg_gs_color_fixed3<2, A, B, C><<<grd, blk, 0, s>>>(d, col, K, ks, scale, u, b, mk, forward)
-            const int key = (col.start[0] == 1 ? 0 : 4) + (col.start[1] == 1 ? 0 : 2) + (col.start[2] == 1 ? 0 : 1);
-            switch (key) {
-                case 0: VFEM_GSF(1, 1, 1); break;
-                case 1: VFEM_GSF(1, 1, 2); break;
-                case 2: VFEM_GSF(1, 2, 1); break;
-                case 3: VFEM_GSF(1, 2, 2); break;
-                case 4: VFEM_GSF(2, 1, 1); break;
-                case 5: VFEM_GSF(2, 1, 2); break;
-                case 6: VFEM_GSF(2, 2, 1); break;
-                default: VFEM_GSF(2, 2, 2);
-            }
-#undef VFEM_GSF
-        }
+        if (d.N == 3 && d.p == 2)      // incident elements per axis: 1 for a mid node (local index 1), 2 for a node on an element boundary
+            with_bits3(7 - parity_bits(col), [&](auto A, auto B, auto C) {
+                kg_gs_color_fixed3<2, 1 + A.value, 1 + B.value, 1 + C.value><<<grd, blk, 0, s>>>(d, col, K, ks, scale, u, b, mk, forward);
+            });
         else if (d.N == 3) kg_gs_color<3, 1><<<grd, blk, 0, s>>>(d, col, K, ks, scale, u, b, mk, forward);
         else if (d.p == 2) kg_gs_color<2, 2><<<grd, blk, 0, s>>>(d, col, K, ks, scale, u, b, mk, forward);
         else kg_gs_color<2, 1><<<grd, blk, 0, s>>>(d, col, K, ks, scale, u, b, mk, forward);
-    }
+    });
     VFEM_HIP(hipGetLastError());
 }
 
@@ -925,10 +876,6 @@ static void gmg_prolong(vfem_gmg *mg, int l, const double *coarse, double *fine,
 static void g_dirichlet(const GDims &d, const uint8_t *mask, const double *vals, double *u, hipStream_t s) {
     kg_dirichlet<<<dim3((unsigned) ((d.nnodes * d.N + 255) / 256)), dim3(256), 0, s>>>(d.nnodes, d.N, mask, vals, u);
     VFEM_HIP(hipGetLastError());
-}
-static void gmg_coarsest(vfem_gmg *mg, const double *b, double *x, hipStream_t s) {
-    if (!mg->Ainv.p) throw Error("coarsest grid too large for the dense coarsest-level solve; use more coarsening levels");
-    launch_gemv_sym((long long) mg->lv[mg->L].d.N * mg->lv[mg->L].d.nnodes, mg->Ainv.p, b, x, s);
 }
 
 // Galerkin element matrices of the coarse elements `c` from their 2^N children in `f` (buildPESCoarse, MG.hh:604-669);
@@ -998,15 +945,15 @@ static void gmg_update(vfem_gmg *mg, hipStream_t s) {
         g_coarsen(mg, fd, cd, from_moduli, from_moduli ? sim->E.p : mg->lv[l - 1].Ke.p, lv.Ke.p, s);
     }
     if (mg->slab) { mg->operators_valid = true; return; }
-    // coarsest level: assemble the dense matrix on the host (a few elements), invert with rocSOLVER
+    // coarsest level: assemble the dense matrix on the host (a few elements), invert on the device (dense_spd.hip)
     GLevel &cl = mg->lv[mg->L];
     const GDims &d = cl.d;
     const long long n = (long long) N * d.nnodes;
-    if (n > 40000) {
-        // a grid that cannot be coarsened (odd element counts) and is too large for the dense factorisation can still be
-        // solved by the unpreconditioned CG (mgSmoothingIterations = 0, MG.hh:476-479); any cycle on it throws
-        if (mg->L > 0) throw Error("coarsest grid too large for the dense coarsest-level solve (" + std::to_string(n) + " dofs); use more coarsening levels");
-        mg->Ainv.release();
+    // a grid that cannot be coarsened (odd element counts) and is too large for the dense factorisation can still be
+    // solved by the unpreconditioned CG (mgSmoothingIterations = 0, MG.hh:476-479); any cycle on it throws
+    if (mg->L > 0) mg->coarsest.refuse_if_too_large(n, nullptr);
+    else if (n > DENSE_COARSEST_MAX_DOFS) {
+        mg->coarsest.release();
         mg->operators_valid = true;
         return;
     }
@@ -1043,12 +990,10 @@ static void gmg_update(vfem_gmg *mg, hipStream_t s) {
             for (long long c = 0; c < n; ++c) { A[(size_t) r * n + c] = 0.0; A[(size_t) c * n + r] = 0.0; }
             A[(size_t) r * n + r] = 1.0;
         }
-    mg->Ainv.alloc((size_t) n * n);
+    double *Adev = mg->coarsest.dense_matrix(n, s);
     VFEM_HIP(hipStreamSynchronize(s));
-    VFEM_HIP(hipMemcpy(mg->Ainv.p, A.data(), A.size() * sizeof(double), hipMemcpyHostToDevice));       // (synchronous: the source is pageable host memory)
-    dense_spd_inverse(n, mg->Ainv.p, mg->dense, s);      // own kernels, fixed summation order (dense_spd.hip)
-    kg_dense_finish<<<dim3((unsigned) ((n * n + 255) / 256)), dim3(256), 0, s>>>(n, N, cl.mask.p, mg->Ainv.p);
-    VFEM_HIP(hipGetLastError());
+    VFEM_HIP(hipMemcpy(Adev, A.data(), A.size() * sizeof(double), hipMemcpyHostToDevice));       // (synchronous: the source is pageable host memory)
+    mg->coarsest.factor_dense(N, cl.mask.p, s);
     VFEM_HIP(hipStreamSynchronize(s));
     mg->operators_valid = true;
 }
@@ -1061,7 +1006,7 @@ struct GenericOps {
     GLevel &lv(int l) const { return mg->lv[l]; }
 
     int last_level() const { return mg->L; }
-    void last_level_cycle(bool) { gmg_coarsest(mg, b(mg->L), x(mg->L), s); }
+    void last_level_cycle(bool) { mg->coarsest.solve(b(mg->L), x(mg->L), s); }
     bool symmetric() const { return mg->symmetric_gs; }
     double *x(int l) const { return lv(l).x.p; }
     double *b(int l) const { return lv(l).b.p; }
@@ -1408,13 +1353,8 @@ int vfem_gmg_cycle_from_level(vfem_gmg *mg, int level, double *x, const double *
     if (mg->slab) throw Error("slab hierarchies are cycled by the distributed driver");
     if (!mg->operators_valid) throw Error("coarse operators not built: call vfem_gmg_update_operators first");
     hipStream_t s = S(stream);
-    GLevel &L = mg->lv[level];
-    const size_t bytes = (size_t) L.d.nnodes * L.d.N * sizeof(double);
-    VFEM_HIP(hipMemcpyAsync(L.b.p, b, bytes, hipMemcpyDeviceToDevice, s));
-    if (!fmg) VFEM_HIP(hipMemcpyAsync(L.x.p, x, bytes, hipMemcpyDeviceToDevice, s));
     GenericOps o{mg, s};
-    mg_cycle::cycles(o, level, 1, nsmooth, true, fmg != 0);
-    VFEM_HIP(hipMemcpyAsync(x, L.x.p, bytes, hipMemcpyDeviceToDevice, s));
+    mg_cycle::cycles_on(o, level, (long long) mg->lv[level].d.N * mg->lv[level].d.nnodes, x, b, 1, nsmooth, true, fmg != 0, s);
     VFEM_CATCH
 }
 // Galerkin element matrices of `count_x` element layers of `level` computed from their children, which start at stored layer
@@ -1469,12 +1409,8 @@ int vfem_gmg_solve(vfem_gmg *mg, double *x, const double *f, int num_steps, int 
     if (!stiffness_updated) gmg_update(mg, s);                         // MG.hh:455
     else if (!mg->operators_valid) throw Error("coarse operators not built");
     if (num_steps == 0) return 0;
-    const size_t bytes = (size_t) mg->fine->d.nnodes * mg->fine->d.N * sizeof(double);
-    VFEM_HIP(hipMemcpyAsync(mg->lv[0].x.p, x, bytes, hipMemcpyDeviceToDevice, s));
-    VFEM_HIP(hipMemcpyAsync(mg->lv[0].b.p, f, bytes, hipMemcpyDeviceToDevice, s));
     GenericOps o{mg, s};
-    mg_cycle::cycles(o, 0, num_steps, nsmooth, zero_dirichlet != 0, fmg != 0);
-    VFEM_HIP(hipMemcpyAsync(x, mg->lv[0].x.p, bytes, hipMemcpyDeviceToDevice, s));
+    mg_cycle::cycles_on(o, 0, o.n_dofs(), x, f, num_steps, nsmooth, zero_dirichlet != 0, fmg != 0, s);
     VFEM_CATCH
 }
 int vfem_gmg_pcg(vfem_gmg *mg, double *x, const double *b, int max_iter, double tol, int mg_iterations, int mg_smoothing,

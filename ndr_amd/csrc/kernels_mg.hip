@@ -1565,19 +1565,19 @@ void launch_plane_rows_from_stencil(const Dims &d, const double *S, const uint8_
     VFEM_HIP(hipGetLastError());
 }
 
-// after potrf+potri(lower, column-major == upper, row-major): mirror the computed triangle and zero the
-// rows/columns of fixed dofs so that x_fixed = 0 and rhs_fixed is ignored.
-__global__ void __launch_bounds__(256) k_dense_finish(long long n, const uint8_t *__restrict__ mask, double *__restrict__ A) {
+// after dense_spd_inverse, which leaves the full symmetric inverse: zero the rows / columns of fixed dofs so that x_fixed = 0 and
+// rhs_fixed is ignored, and copy the upper triangle over the lower one.  N: components per node (the mask holds a bit each)
+__global__ void __launch_bounds__(256) k_dense_finish(long long n, int N, const uint8_t *__restrict__ mask, double *__restrict__ A) {
     const long long gid = (long long) blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= n * n) return;
     const long long r = gid / n, c = gid % n;
-    const bool fr = (mask[r / 3] >> (r % 3)) & 1, fc = (mask[c / 3] >> (c % 3)) & 1;
+    const bool fr = (mask[r / N] >> (r % N)) & 1, fc = (mask[c / N] >> (c % N)) & 1;
     if (fr || fc) { A[gid] = 0.0; return; }
     if (c < r) A[gid] = A[c * n + r];   // row-major upper triangle (c >= r) holds the result
 }
 
-void launch_dense_finish_inverse(long long n, const uint8_t *mask, double *A, hipStream_t s) {
-    k_dense_finish<<<dim3((unsigned) ((n * n + 255) / 256)), dim3(256), 0, s>>>(n, mask, A);
+void launch_dense_finish_inverse(long long n, int N, const uint8_t *mask, double *A, hipStream_t s) {
+    k_dense_finish<<<dim3((unsigned) ((n * n + 255) / 256)), dim3(256), 0, s>>>(n, N, mask, A);
     VFEM_HIP(hipGetLastError());
 }
 

@@ -10,6 +10,7 @@
 #include "vfem_internal.h"
 #include "device_utils.h"
 #include "q2_modes.h"
+#include "gs_colors.h"
 
 namespace vfem {
 
@@ -628,7 +629,7 @@ void launch_apply_q2_march(int nx, int ny, int nz, const double *tab, const doub
 // element for the mid node, by two for a boundary node).  All nodes of a colour have the same local index in each of their
 // incident elements, so the rows of K0 are wave-uniform.
 // ------------------------------------------------------------------------------------------------------
-struct Q2Color { int start[3], inc[3], cnt[3]; };
+struct Q2Color : GsColor {};          // (the kernels' parameter type: its name is part of their symbols)
 
 template <int PX, int PY, int PZ>      // node parities of the colour (odd = mid node of one element) at compile time: the slot loops unroll
 __global__ void __launch_bounds__(256) k_gs_q2_level0(DimsQ2 d, Q2Color col, const double *__restrict__ K0, const double *__restrict__ E,
@@ -696,32 +697,13 @@ void launch_gs_sweep_q2_level0(int nx, int ny, int nz, const double *K0, const d
                                const uint8_t *mask, int forward, hipStream_t s, int first, int count) {
     DimsQ2 d{nx, ny, nz, 2 * nx + 1, 2 * ny + 1, 2 * nz + 1};
     const int NN[3] = {d.NX, d.NY, d.NZ};
-    for (int ci = first; ci < (first + count < 27 ? first + count : 27); ++ci) {
-        const int lni = forward ? ci : 26 - ci;                      // MG.hh:293-295
-        const int l[3] = {lni / 9, (lni / 3) % 3, lni % 3};
-        Q2Color col;
-        bool empty = false;
-        for (int a = 0; a < 3; ++a) {
-            col.start[a] = l[a];
-            col.inc[a] = (l[a] == 1) ? 2 : 4;                        // MG.hh:301-305: (1 + isBoundary) * degree
-            col.cnt[a] = l[a] > NN[a] - 1 ? 0 : (NN[a] - 1 - l[a]) / col.inc[a] + 1;
-            empty = empty || col.cnt[a] == 0;
-        }
-        if (empty) continue;
+    for_each_gs_color(3, 2, NN, forward, first, count, [&](const GsColor &gc) {
+        const Q2Color col{gc};
         const dim3 grd((col.cnt[2] + 63) / 64, (col.cnt[1] + 3) / 4, col.cnt[0]), blk(64, 4, 1);
-#define VFEM_Q2GS(X, Y, Z) k_gs_q2_level0<X, Y, Z><<<grd, blk, 0, s>>>(d, col, K0, E, u, b, mask, forward)
-        switch (4 * (l[0] & 1) + 2 * (l[1] & 1) + (l[2] & 1)) {
-            case 0: VFEM_Q2GS(0, 0, 0); break;
-            case 1: VFEM_Q2GS(0, 0, 1); break;
-            case 2: VFEM_Q2GS(0, 1, 0); break;
-            case 3: VFEM_Q2GS(0, 1, 1); break;
-            case 4: VFEM_Q2GS(1, 0, 0); break;
-            case 5: VFEM_Q2GS(1, 0, 1); break;
-            case 6: VFEM_Q2GS(1, 1, 0); break;
-            default: VFEM_Q2GS(1, 1, 1);
-        }
-#undef VFEM_Q2GS
-    }
+        with_bits3(parity_bits(col), [&](auto X, auto Y, auto Z) {
+            k_gs_q2_level0<X.value, Y.value, Z.value><<<grd, blk, 0, s>>>(d, col, K0, E, u, b, mask, forward);
+        });
+    });
     VFEM_HIP(hipGetLastError());
 }
 
@@ -988,19 +970,9 @@ void launch_gs_sweep_q2_level0_nodes(int nx, int ny, int nz, const double *tab, 
                                      const uint8_t *mask, int forward, hipStream_t s, int first, int count, int rows_in_lds) {
     DimsQ2 d{nx, ny, nz, 2 * nx + 1, 2 * ny + 1, 2 * nz + 1};
     const int NN[3] = {d.NX, d.NY, d.NZ};
-    for (int ci = first; ci < (first + count < 27 ? first + count : 27); ++ci) {
-        const int lni = forward ? ci : 26 - ci;                      // MG.hh:293-295
-        const int l[3] = {lni / 9, (lni / 3) % 3, lni % 3};
-        Q2Color col;
-        bool empty = false;
-        for (int a = 0; a < 3; ++a) {
-            col.start[a] = l[a];
-            col.inc[a] = (l[a] == 1) ? 2 : 4;                        // MG.hh:301-305
-            col.cnt[a] = l[a] > NN[a] - 1 ? 0 : (NN[a] - 1 - l[a]) / col.inc[a] + 1;
-            empty = empty || col.cnt[a] == 0;
-        }
-        if (empty) continue;
-        const int cls = 4 * (l[0] & 1) + 2 * (l[1] & 1) + (l[2] & 1);
+    for_each_gs_color(3, 2, NN, forward, first, count, [&](const GsColor &gc) {
+        const Q2Color col{gc};
+        const int cls = parity_bits(col);
         const double *tc = tab + q2_table_offset(cls);
         // rows kernel: whole waves of 64 nodes per z-row; a row of 2^k + 1 nodes leaves one node over, and a wave for it would
         // run the full stream with one lane: the left-over columns (up to 16 per row) go to the gather kernel, lanes packed
@@ -1016,20 +988,11 @@ void launch_gs_sweep_q2_level0_nodes(int nx, int ny, int nz, const double *tab, 
         const Q2Color &coln = split ? coll : col;
         const dim3 grd((coln.cnt[1] * coln.cnt[2] + 255) / 256, 1, coln.cnt[0]), blk(64, 4, 1);
         const dim3 grdr((colr.cnt[2] + 63) / 64, (colr.cnt[1] + VFEM_Q2ROWS_WAVES - 1) / VFEM_Q2ROWS_WAVES, colr.cnt[0]), blkr(64, VFEM_Q2ROWS_WAVES, 1);
-#define VFEM_Q2GSN(X, Y, Z) do { if (rows_in_lds) k_gs_q2_level0_rows<X, Y, Z><<<grdr, blkr, 0, s>>>(d, colr, tc, E, u, b, mask, forward); \
-                                if (!rows_in_lds || split) k_gs_q2_level0_nodes<X, Y, Z><<<grd, blk, 0, s>>>(d, coln, tc, E, u, b, mask, forward); } while (0)
-        switch (cls) {
-            case 0: VFEM_Q2GSN(0, 0, 0); break;
-            case 1: VFEM_Q2GSN(0, 0, 1); break;
-            case 2: VFEM_Q2GSN(0, 1, 0); break;
-            case 3: VFEM_Q2GSN(0, 1, 1); break;
-            case 4: VFEM_Q2GSN(1, 0, 0); break;
-            case 5: VFEM_Q2GSN(1, 0, 1); break;
-            case 6: VFEM_Q2GSN(1, 1, 0); break;
-            default: VFEM_Q2GSN(1, 1, 1);
-        }
-#undef VFEM_Q2GSN
-    }
+        with_bits3(cls, [&](auto X, auto Y, auto Z) {
+            if (rows_in_lds) k_gs_q2_level0_rows<X.value, Y.value, Z.value><<<grdr, blkr, 0, s>>>(d, colr, tc, E, u, b, mask, forward);
+            if (!rows_in_lds || split) k_gs_q2_level0_nodes<X.value, Y.value, Z.value><<<grd, blk, 0, s>>>(d, coln, tc, E, u, b, mask, forward);
+        });
+    });
     VFEM_HIP(hipGetLastError());
 }
 
@@ -1203,21 +1166,12 @@ void launch_gs_sweep_q2_level1(int nx, int ny, int nz, const double *tab, const 
                                const uint8_t *mask, int forward, hipStream_t s, int first, int count) {
     Q2L1 a = q2l1_args(nx, ny, nz, tab, Ef, fx0);
     const int NN[3] = {a.d.NX, a.d.NY, a.d.NZ};
-    for (int ci = first; ci < (first + count < 27 ? first + count : 27); ++ci) {
-        const int lni = forward ? ci : 26 - ci;                      // MG.hh:293-295
-        const int l[3] = {lni / 9, (lni / 3) % 3, lni % 3};
-        bool empty = false;
-        for (int ax = 0; ax < 3; ++ax) {
-            a.col.start[ax] = l[ax];
-            a.col.inc[ax] = (l[ax] == 1) ? 2 : 4;                    // MG.hh:301-305
-            a.col.cnt[ax] = l[ax] > NN[ax] - 1 ? 0 : (NN[ax] - 1 - l[ax]) / a.col.inc[ax] + 1;
-            empty = empty || a.col.cnt[ax] == 0;
-        }
-        if (empty) continue;
-        const int waves = (l[0] == 1 ? 1 : 2) * (l[1] == 1 ? 1 : 2) * (l[2] == 1 ? 1 : 2);
+    for_each_gs_color(3, 2, NN, forward, first, count, [&](const GsColor &gc) {
+        a.col = Q2Color{gc};
+        const int waves = (gc.start[0] == 1 ? 1 : 2) * (gc.start[1] == 1 ? 1 : 2) * (gc.start[2] == 1 ? 1 : 2);
         const dim3 grd((a.col.cnt[1] * a.col.cnt[2] + 63) / 64, 1, a.col.cnt[0]), blk(64, waves, 1);
         k_q2_level1_gs<<<grd, blk, waves > 1 ? (size_t) waves * 12 * 64 * sizeof(double) : 0, s>>>(a, u, b, mask, forward);
-    }
+    });
     VFEM_HIP(hipGetLastError());
 }
 // mode 0: out = K u; 1: out = zeroDirichlet(b - K u); 2: out = zeroDirichlet(K u) -- one launch per node-parity class

@@ -202,10 +202,28 @@ bool vfem::mg_smooth_half(vfem_mg *mg, int l, double *u, const double *b, int fo
     return true;
 }
 
-static void coarsest_solve(vfem_mg *mg, const double *b, double *x, hipStream_t s) {
-    if (mg->coarsest_planes) { plane_spd_solve(mg->planes, b, x, s); return; }
-    const long long n = 3 * mg->lv[mg->L].d.nn;
-    launch_gemv_sym(n, mg->Ainv.p, b, x, s);
+// coarsest level: dense inverse, or the plane-block factorisation (plane_spd.hip) where the mode asks for it -- auto: above the
+// dense path's limit.  Both refuse before anything is allocated
+static void factor_coarsest(vfem_mg *mg, hipStream_t s) {
+    const int L = mg->L;
+    MgLevel &cl = mg->lv[L];
+    CoarsestSolver &cs = mg->coarsest;
+    const long long n = 3 * cl.d.nn;
+    const bool planes = cs.wants_planes(n);
+    cs.refuse_if_too_large(n, planes ? &cl.d : nullptr);
+    const double *Sc = cl.S.p;
+    DevBuf<double> tmpS;
+    if (L < 2) {
+        tmpS.alloc((size_t) stencil_storage_doubles(cl.d));
+        launch_stencil_from_mf(cl.d, L == 0 ? OP_MF0 : OP_MF1, level_K(mg, L), level_E(mg, L), tmpS.p, s);
+        Sc = tmpS.p;
+    }
+    if (planes) cs.factor_planes(cl.d, Sc, cl.maskp, s);
+    else {
+        launch_dense_from_stencil(cl.d, Sc, cl.maskp, cs.dense_matrix(n, s), s);
+        cs.factor_dense(3, cl.maskp, s);
+    }
+    VFEM_HIP(hipStreamSynchronize(s));   // tmpS lifetime
 }
 
 void vfem::update_operators(vfem_mg *mg, hipStream_t s) {
@@ -253,45 +271,7 @@ void vfem::update_operators(vfem_mg *mg, hipStream_t s) {
             launch_stencil_node_major(lv.d, lv.S.p, lv.Sn.p, s);
         } else lv.Sn.release();
     }
-    if (mg->slab) { mg->operators_valid = true; mg->operators_version = sim->operator_version; return; }       // the coarse levels live in the replicated hierarchy
-    // coarsest level: dense inverse, or the plane-block factorisation (plane_spd.hip) where the mode asks for it -- auto: above the
-    // dense path's limit.  Both refuse before anything is allocated
-    MgLevel &cl = mg->lv[L];
-    const long long n = 3 * cl.d.nn;
-    const bool planes = mg->coarsest_mode == VFEM_COARSEST_PLANES || (mg->coarsest_mode == VFEM_COARSEST_AUTO && n > 40000);
-    if (planes ? plane_spd_bytes_needed(cl.d) > PLANE_SPD_MAX_BYTES : n > 40000)
-        throw Error("coarsest grid too large for the " + std::string(planes ? "plane-block" : "dense") + " coarsest-level solve (" +
-                    std::to_string(n) + " dofs); use more coarsening levels");
-    const double *Sc = cl.S.p;
-    DevBuf<double> tmpS;
-    if (L < 2) {
-        tmpS.alloc((size_t) stencil_storage_doubles(cl.d));
-        launch_stencil_from_mf(cl.d, L == 0 ? OP_MF0 : OP_MF1, level_K(mg, L), level_E(mg, L), tmpS.p, s);
-        Sc = tmpS.p;
-    }
-    if (planes) {
-        mg->Ainv.release();
-        plane_spd_factor(mg->planes, cl.d, Sc, cl.maskp, mg->dense, s);
-        VFEM_HIP(hipStreamSynchronize(s));   // tmpS lifetime
-        mg->coarsest_planes = true;
-        mg->operators_valid = true;
-        mg->operators_version = sim->operator_version;
-        return;
-    }
-    mg->planes.release();
-    mg->coarsest_planes = false;
-    mg->Ainv.alloc((size_t) n * n);
-    mg->Ainv.zero(s);
-    launch_dense_from_stencil(cl.d, Sc, cl.maskp, mg->Ainv.p, s);
-    dense_spd_inverse(n, mg->Ainv.p, mg->dense, s);      // own kernels, fixed summation order (dense_spd.hip)
-    // three further n x n work matrices: kept between operator updates while they are small (2 187 dofs: 115 MB), released when the
-    // coarsest level is large -- they would otherwise be held for the hierarchy's lifetime at three times the inverse's size
-    if ((size_t) n * (size_t) n * sizeof(double) > ((size_t) 256 << 20)) {
-        VFEM_HIP(hipStreamSynchronize(s));
-        mg->dense.L.release(); mg->dense.X.release(); mg->dense.Tm.release();
-    }
-    launch_dense_finish_inverse(n, cl.maskp, mg->Ainv.p, s);
-    VFEM_HIP(hipStreamSynchronize(s));   // tmpS lifetime
+    if (!mg->slab) factor_coarsest(mg, s);            // (a slab's coarse levels live in the replicated hierarchy)
     mg->operators_valid = true;
     mg->operators_version = sim->operator_version;
 }
@@ -304,7 +284,7 @@ struct TunedOps {
     MgLevel &lv(int l) const { return mg->lv[(size_t) l]; }
 
     int last_level() const { return mg->L; }
-    void last_level_cycle(bool) { coarsest_solve(mg, lv(mg->L).b.p, lv(mg->L).x.p, s); }
+    void last_level_cycle(bool) { mg->coarsest.solve(lv(mg->L).b.p, lv(mg->L).x.p, s); }
     bool symmetric() const { return mg->symmetric_gs; }
     double *x(int l) const { return lv(l).x.p; }
     double *b(int l) const { return lv(l).b.p; }
@@ -589,20 +569,17 @@ int vfem_mg_interpolate(vfem_mg *mg, int fine_level, const double *coarse, doubl
 int vfem_mg_coarsest_solve(vfem_mg *mg, const double *b, double *x, void *stream) {
     VFEM_TRY
     update_operators(mg, S(stream));
-    coarsest_solve(mg, b, x, S(stream));
+    mg->coarsest.solve(b, x, S(stream));
     VFEM_CATCH
 }
 int vfem_mg_set_coarsest_solver(vfem_mg *mg, int mode) {
     VFEM_TRY
-    if (mode != VFEM_COARSEST_AUTO && mode != VFEM_COARSEST_DENSE && mode != VFEM_COARSEST_PLANES)
-        throw Error("unknown coarsest-level solver mode " + std::to_string(mode));
-    if (mode != mg->coarsest_mode) mg->operators_valid = false;      // the kept factorisation belongs to the old mode
-    mg->coarsest_mode = mode;
+    if (mg->coarsest.set_mode(mode)) mg->operators_valid = false;      // the kept factorisation belongs to the old mode
     VFEM_CATCH
 }
 int64_t vfem_mg_coarsest_bytes(const vfem_mg *mg) {
     if (!mg->operators_valid || mg->slab) return 0;
-    return mg->coarsest_planes ? mg->planes.bytes() : (int64_t) (mg->Ainv.n * sizeof(double));
+    return mg->coarsest.bytes();
 }
 
 int vfem_mg_smooth_colors(vfem_mg *mg, int level, double *u, const double *b, int forward, int first, int count, void *stream) {
@@ -639,12 +616,8 @@ int vfem_mg_cycle_from_level(vfem_mg *mg, int level, double *x, const double *b,
     if (mg->slab) throw Error("slab hierarchies are cycled by the distributed driver");
     hipStream_t s = S(stream);
     update_operators(mg, s);
-    MgLevel &L = mg->lv[(size_t) level];
-    const size_t bytes = (size_t) L.d.nn * 3 * sizeof(double);
-    VFEM_HIP(hipMemcpyAsync(L.b.p, b, bytes, hipMemcpyDeviceToDevice, s));
-    if (!fmg) VFEM_HIP(hipMemcpyAsync(L.x.p, x, bytes, hipMemcpyDeviceToDevice, s));
-    cycle_from_level(mg, level, nsmooth, fmg != 0, s);
-    VFEM_HIP(hipMemcpyAsync(x, L.x.p, bytes, hipMemcpyDeviceToDevice, s));
+    TunedOps o{mg, s};
+    mg_cycle::cycles_on(o, level, 3 * mg->lv[(size_t) level].d.nn, x, b, 1, nsmooth, true, fmg != 0, s);
     VFEM_CATCH
 }
 
@@ -656,12 +629,8 @@ int vfem_mg_solve(vfem_mg *mg, double *x, const double *f, int num_steps, int ns
     (void) stiffness_updated;                       // the simulator tracks changes of the moduli itself
     update_operators(mg, s);
     if (num_steps == 0) return 0;
-    const size_t bytes = (size_t) mg->fine->d.nn * 3 * sizeof(double);
-    VFEM_HIP(hipMemcpyAsync(mg->lv[0].x.p, x, bytes, hipMemcpyDeviceToDevice, s));
-    VFEM_HIP(hipMemcpyAsync(mg->lv[0].b.p, f, bytes, hipMemcpyDeviceToDevice, s));
     TunedOps o{mg, s};
-    mg_cycle::cycles(o, 0, num_steps, nsmooth, zero_dirichlet != 0, fmg != 0);
-    VFEM_HIP(hipMemcpyAsync(x, mg->lv[0].x.p, bytes, hipMemcpyDeviceToDevice, s));
+    mg_cycle::cycles_on(o, 0, o.n_dofs(), x, f, num_steps, nsmooth, zero_dirichlet != 0, fmg != 0, s);
     VFEM_CATCH
 }
 

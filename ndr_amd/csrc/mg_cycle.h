@@ -57,6 +57,17 @@ template <class Ops> void cycles(Ops &o, int l, int n, int nsmooth, bool residua
     for (int i = fmg ? 1 : 0; i < n; ++i) vcycle(o, l, nsmooth, residual_system);
 }
 
+// what an entry point does with the caller's vectors of level l (n dofs): b, and x unless full multigrid overwrites it, into the
+// level's work vectors, the cycles, x back out.  Stream-ordered
+template <class Ops>
+void cycles_on(Ops &o, int l, long long n, double *x, const double *b, int cycles_n, int nsmooth, bool residual_system, bool fmg, hipStream_t s) {
+    const size_t bytes = (size_t) n * sizeof(double);
+    VFEM_HIP(hipMemcpyAsync(o.b(l), b, bytes, hipMemcpyDeviceToDevice, s));
+    if (!fmg) VFEM_HIP(hipMemcpyAsync(o.x(l), x, bytes, hipMemcpyDeviceToDevice, s));
+    cycles(o, l, cycles_n, nsmooth, residual_system, fmg);
+    VFEM_HIP(hipMemcpyAsync(x, o.x(l), bytes, hipMemcpyDeviceToDevice, s));
+}
+
 // MG.hh:696-732 (x has its Dirichlet values, the operators are current).  The residual lives in b(0) and the preconditioned
 // residual is read from x(0): no cycle writes b(0), so neither vector is copied in or out (2 x 3.2 GB per iteration at 512^3).
 template <class Ops>

@@ -137,7 +137,7 @@ void plane_spd_factor(PlaneSolver &ps, const Dims &d, const double *S, const uin
         VFEM_HIP(hipGetLastError());
         try { dense_spd_inverse(m, Tj, w, s); }          // synchronises s for its pivot check
         catch (const Error &e) { throw Error(std::string(e.what()) + " in x plane " + std::to_string(j) + " of " + std::to_string(d.NX)); }
-        launch_dense_finish_inverse(m, mask + (size_t) j * plane_nodes, Tj, s);
+        launch_dense_finish_inverse(m, 3, mask + (size_t) j * plane_nodes, Tj, s);
     }
 }
 

@@ -175,7 +175,8 @@ long long stencil_storage_doubles(const Dims &d);            // size of a level'
 void launch_stencil_from_ke(const Dims &d, const double *Ke, double *S, hipStream_t s);
 void launch_stencil_from_mf(const Dims &d, OpKind kind, const double *K, const double *E, double *S, hipStream_t s);
 void launch_dense_from_stencil(const Dims &d, const double *S, const uint8_t *mask, double *A, hipStream_t s);
-void launch_dense_finish_inverse(long long n, const uint8_t *mask, double *A, hipStream_t s);
+// what both coarsest-level factorisations end with: rows / columns of the fixed dofs of an inverse zeroed (N components per node)
+void launch_dense_finish_inverse(long long n, int N, const uint8_t *mask, double *A, hipStream_t s);
 // node-major rows of the same matrix (fixed rows / columns replaced by identity), [nn][27][9]: what plane_spd.hip keeps
 void launch_plane_rows_from_stencil(const Dims &d, const double *S, const uint8_t *mask, double *R, hipStream_t s);
 void launch_gemv_sym(long long n, const double *A, const double *x, double *y, hipStream_t s);
@@ -234,6 +235,28 @@ long long plane_spd_bytes_needed(const Dims &d);           // T, R, W, the vecto
 // S: the level's colour-major stencil.  Synchronises s (once per plane: the pivot check of dense_spd_inverse)
 void plane_spd_factor(PlaneSolver &ps, const Dims &d, const double *S, const uint8_t *mask, DenseWork &w, hipStream_t s);
 void plane_spd_solve(PlaneSolver &ps, const double *b, double *x, hipStream_t s);        // stream-ordered, 4 NX - 3 launches
+// The exact solve of a hierarchy's coarsest level (coarsest.hip; host code): the dense inverse applied as a GEMV or the plane-block
+// factorisation, with their workspace.  The hierarchy assembles the operator and says which solver; everything else is here.
+constexpr long long DENSE_COARSEST_MAX_DOFS = 40000;      // n = 40 000: 12.8 GB + three work matrices of the padded size = 51 GB
+struct CoarsestSolver {
+    int mode = VFEM_COARSEST_AUTO;                          // VFEM_COARSEST_AUTO / _DENSE / _PLANES (vfem_mg_set_coarsest_solver)
+    enum Held { NONE, DENSE, PLANES } held = NONE;          // the factorisation solve() applies
+    long long n = 0;                                        // its dofs
+    DevBuf<double> Ainv;                                    // n x n inverse
+    DenseWork work;                                         // dense_spd_inverse's workspace (the plane blocks are inverted with it too)
+    PlaneSolver planes;
+    bool set_mode(int m);                                   // true: the mode changed, so the factorisation held is the wrong one.  Throws on an unknown mode
+    bool wants_planes(long long dofs) const { return mode == VFEM_COARSEST_PLANES || (mode == VFEM_COARSEST_AUTO && dofs > DENSE_COARSEST_MAX_DOFS); }
+    // throws when the solver cannot take the level: the plane blocks of grid *plane_grid, or (null) the dense inverse of `dofs`.
+    // Call it before anything of the update is allocated
+    void refuse_if_too_large(long long dofs, const Dims *plane_grid) const;
+    double *dense_matrix(long long dofs, hipStream_t s);    // dofs x dofs zeros for the caller to write the operator into (fixed rows / columns: identity)
+    void factor_dense(int N, const uint8_t *mask, hipStream_t s);       // ... and its inverse in place; N components per node of the mask
+    void factor_planes(const Dims &d, const double *S, const uint8_t *mask, hipStream_t s);     // as plane_spd_factor
+    void solve(const double *b, double *x, hipStream_t s);  // throws when no factorisation is held (a level nothing could factorise)
+    long long bytes() const { return held == PLANES ? planes.bytes() : (long long) (Ainv.n * sizeof(double)); }
+    void release() { held = NONE; Ainv.release(); planes.release(); work = DenseWork(); }
+};
 void launch_gs_sweep_q2_level1(int nx, int ny, int nz, const double *cK0, const double *Ef, int fx0, double *u, const double *b,
                                const uint8_t *mask, int forward, hipStream_t s, int first = 0, int count = 27);
 void launch_apply_q2_level1(int nx, int ny, int nz, const double *cK0, const double *Ef, int fx0, const double *u, const double *b,
@@ -338,7 +361,6 @@ struct vfem_mg {
     vfem::DevBuf<double> mf1diag;               // 8 x 12: diagonal blocks of cK0[0] (level-1 Gauss-Seidel)
     vfem::DevBuf<double> l1mtab;                // cK0[0] by mirror class (build_l1_merged_table)
     vfem::DevBuf<double> c2K0;                  // 64 x 576: I_g^T cK0[f] I_g (level-2 element matrices from the fine moduli)
-    vfem::DevBuf<double> Ainv;                  // coarsest-level dense inverse
     vfem::DevBuf<double> pd, pAd, ps;           // PCG vectors (the residual lives in lv[0].b)
     vfem::DevBuf<double> scal, scratch;
     bool slab = false;                          // local part of an x-slab decomposition: no coarsest solver here
@@ -348,10 +370,7 @@ struct vfem_mg {
     bool operators_valid = false;
     long long operators_version = 0;            // fine->operator_version the coarse operators were built for
     bool mf1_sym = false;                       // cK0[f] are mirror images of cK0[0]: level-1 sweeps read cK0[0] only
-    vfem::DenseWork dense;                      // workspace of the coarsest-level inverse
-    int coarsest_mode = 0;                      // VFEM_COARSEST_AUTO / _DENSE / _PLANES (vfem_mg_set_coarsest_solver)
-    bool coarsest_planes = false;               // the factorisation held is the plane-block one (planes), not Ainv
-    vfem::PlaneSolver planes;                   // coarsest-level plane-block factorisation (plane_spd.hip)
+    vfem::CoarsestSolver coarsest;              // exact solve of level L (not in a slab hierarchy)
 };
 
 struct vfem_mlp {

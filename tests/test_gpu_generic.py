@@ -143,6 +143,62 @@ def test_generic_unpreconditioned_cg_matches_oracle(N, p, ne, dom, bc):
     assert err < 1e-7
 
 
+@pytest.mark.parametrize("N,p,ne,dom,bc", [CASES[1], CASES[3]])
+def test_generic_coarsest_solve_matches_oracle(N, p, ne, dom, bc):
+    """no coarsening levels: one cycle is the coarsest-level solve alone (the dense inverse of the whole operator applied to f)"""
+    from oracle import generic_oracle as go
+    t, o = _make(N, p, ne, dom, bc)
+    mg, om = t.multigridSolver(0), go.GenericMG(o, 0)
+    f = np.random.default_rng(6).standard_normal((o.num_nodes, N))
+    xo = om.solve(np.zeros_like(f), f, 1, 2, False, False, False).copy()
+    xg = mg.solve(np.zeros_like(f), f, 1, 2, False, False, None, False)
+    print("coarsest solve <%s> %s: rel %.3e" % (",".join([str(p)] * N), ne, rel(xg, xo)))
+    assert rel(xg, xo) < 1e-9
+    assert o.mask.any() and np.all(xg[o.mask] == 0.0)
+
+
+Q2_LONG = (3, 2, (4, 4, 132), ([0, 0, 0], [1, 1, 33]), BC3D)      # 265 nodes per z row: every colour's row leaves 2-4 nodes over a multiple of 64
+Q2_GS_IMPL, Q2_L1_VIRTUAL = 16, 14                                # VFEM_OPT_* of include/vfem.h
+SPLIT_CASES = ([(c, l, ()) for c in (CASES[0], CASES[1], CASES[3]) for l in (0, 1, 2)] +
+               [(Q2_LONG, 0, ((Q2_GS_IMPL, v),)) for v in (0, 1, 2)] + [(Q2_LONG, 1, ((Q2_L1_VIRTUAL, v),)) for v in (0, 1)] +
+               [(Q2_LONG, 2, ())])
+
+
+@pytest.mark.parametrize("case,level,options", SPLIT_CASES)
+def test_colour_sub_ranges_compose_to_the_whole_sweep(case, level, options):
+    """vfem_gmg_smooth_colors (what the distributed degree-2 solver exchanges halos between): colours [0, k) followed by [k, ncol)
+    are the launches of one whole sweep in the same order on one stream, so the result is the same bit for bit, for every k,
+    forward and backward, on every level and under every kernel choice; ranges outside [0, ncol) are refused"""
+    from ndr_amd import _lib
+    from ndr_amd.pyVoxelFEM import _ptr, _stream
+    N, p, ne, dom, bc = case
+    t, o = _make(N, p, ne, dom, bc)
+    for key, value in options:
+        _lib.check(_lib.load().vfem_gsim_set_option(t._h, key, value))
+    mg = t.multigridSolver(2)
+    assert mg._MG_PREFIX == "vfem_gmg_"
+    mg.updateElementStiffnessMatrices()
+    g = torch.Generator(device="cuda").manual_seed(13)
+    u = torch.randn((mg._nn(level), N), dtype=torch.float64, device="cuda", generator=g)
+    b = torch.randn((mg._nn(level), N), dtype=torch.float64, device="cuda", generator=g)
+    ncol = (p + 1) ** N
+
+    def colours(x, fwd, first, count):
+        _lib.check(mg._mg("smooth_colors")(mg._h, level, _ptr(x), _ptr(b), fwd, first, count, _stream()))
+        return x
+
+    for fwd in (1, 0):
+        whole = colours(u.clone(), fwd, 0, ncol).cpu().numpy()
+        assert np.array_equal(whole, mg.smoothing_device(level, u, b, bool(fwd)).cpu().numpy())
+        assert not np.array_equal(whole, u.cpu().numpy())
+        for k in range(ncol + 1):
+            split = colours(colours(u.clone(), fwd, 0, k), fwd, k, ncol - k).cpu().numpy()
+            assert np.array_equal(split, whole), (fwd, k)
+    for first, count in ((-1, 1), (0, ncol + 1), (ncol, 1), (1, -1)):
+        with pytest.raises(RuntimeError):
+            colours(u.clone(), 1, first, count)
+
+
 def _problem(ne, dom, bc, v0):
     from ndr_amd import pyVoxelFEM as pv
     t = pv.TensorProductSimulator([1, 1], dom, ne)
