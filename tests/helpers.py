@@ -59,6 +59,24 @@ def make_hip(ne, domain, bc, rho=None, v0=0.5, Emin=1e-4):
     return tps
 
 
+def write_cut_bc(path):
+    """a boundary condition that cuts z-rows: all three components on part of the y = 0 face (z below 0.41), the y component on part
+    of the x = max face (z between 0.57 and 0.83), a load on the y = max face: rows of the first level end partway along z on either
+    side of both cuts"""
+    import json
+    regions = [
+        {"type": "dirichlet", "value": [0, 0, 0],
+         "box%": {"minCorner": [-0.0001, -0.0001, -0.0001], "maxCorner": [1.0001, 0.0001, 0.4137]}},
+        {"type": "dirichlety", "value": [0, 0, 0],
+         "box%": {"minCorner": [0.9999, -0.0001, 0.5731], "maxCorner": [1.0001, 1.0001, 0.8263]}},
+        {"type": "force", "value": [0, -1, -0.5],
+         "box%": {"minCorner": [0.2979, 0.9999, -0.0001], "maxCorner": [0.7013, 1.0001, 1.0001]}},
+    ]
+    with open(path, "w") as fh:
+        json.dump({"regions": regions}, fh, indent=1)
+    return str(path)
+
+
 def record_deltas(name, payload):
     """achieved errors of the GPU parity runs, merged into gpurun_out/parity_deltas.json (the summaries judged are copied
     to profiles/); never fails a test"""

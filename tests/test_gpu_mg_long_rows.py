@@ -11,7 +11,6 @@ in z for three of the kernels the production solves run:
 Every parametrisation recomputes the launchers' segment arithmetic and asserts the case it claims, so that a change of shape cannot
 drop the coverage silently (test_shapes_cover_every_branch checks that the claims together reach every branch).  A boundary
 condition that masks rows partway along z (write_cut_bc) is used beside the cantilever's whole-plane one."""
-import json
 import os
 import resource
 import time
@@ -20,7 +19,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import BC_CANTILEVER, make_hip, make_oracle, record_deltas, relerr, seeded_density
+from helpers import BC_CANTILEVER, make_hip, make_oracle, record_deltas, relerr, seeded_density, write_cut_bc
 
 pytestmark = pytest.mark.gpu
 
@@ -91,23 +90,7 @@ def test_shapes_cover_every_branch():
         assert any(c["l1"][fi][0] >= 1 for _, c in SHAPES)
 
 
-# ---- a boundary condition that cuts z-rows -------------------------------------------------------------------------------------------
-def write_cut_bc(path):
-    """all three components on part of the y = 0 face (z below 0.41), the y component on part of the x = max face (z between 0.57 and
-    0.83), a load on the y = max face: rows of the first level end partway along z on either side of both cuts"""
-    regions = [
-        {"type": "dirichlet", "value": [0, 0, 0],
-         "box%": {"minCorner": [-0.0001, -0.0001, -0.0001], "maxCorner": [1.0001, 0.0001, 0.4137]}},
-        {"type": "dirichlety", "value": [0, 0, 0],
-         "box%": {"minCorner": [0.9999, -0.0001, 0.5731], "maxCorner": [1.0001, 1.0001, 0.8263]}},
-        {"type": "force", "value": [0, -1, -0.5],
-         "box%": {"minCorner": [0.2979, 0.9999, -0.0001], "maxCorner": [0.7013, 1.0001, 1.0001]}},
-    ]
-    with open(path, "w") as fh:
-        json.dump({"regions": regions}, fh, indent=1)
-    return str(path)
-
-
+# ---- a boundary condition that cuts z-rows (helpers.write_cut_bc) ------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def cut_bc(tmp_path_factory):
     return write_cut_bc(tmp_path_factory.mktemp("bc") / "cut_rows.bc")
