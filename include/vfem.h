@@ -95,6 +95,26 @@ int64_t vfem_sim_num_elements(const vfem_sim *sim);   /* TPS::numElements, TPS.h
 
 /* ElasticityTensor::setIsotropic via readMaterial/setETensor (TPS.hh:326-339; ElasticityTensor.hh:100-115) */
 int vfem_sim_set_isotropic(vfem_sim *sim, double young, double poisson);
+/* Any elasticity tensor (orthotropic, anisotropic; TPS::ETensor, ElasticityTensor.hh): D is the 6 x 6 flattened tensor, row-major, in
+ * the order xx yy zz yz xz xy of Flattening.hh, holding TENSOR components (a shear row is C_yzyz = mu_yz, no factor 2), so that
+ * C_apbq = D[flat(a,p)][flat(b,q)] and K0[(n,a),(m,b)] = vol sum_pq C_apbq int d_p N_n d_q N_m.  Refused: entries that are not
+ * finite, asymmetry above 1e-10 of the largest entry, a non-positive diagonal entry (positive definiteness is the caller's to check:
+ * ndr_amd.ElasticityTensor does).  Like vfem_sim_set_isotropic it rebuilds K0 and invalidates every operator derived from it; an
+ * existing hierarchy rebuilds its coarsened reference matrices at its next operator update.  vfem_sim_set_isotropic keeps its own
+ * arithmetic: an isotropic D passed here gives the same K0 to rounding, not bit for bit. */
+int vfem_sim_set_elasticity_tensor(vfem_sim *sim, const double D_host[36]);
+/* Which tuned kernels the current K0 runs on: update_k0 verifies numerically what each of them assumes about K0 and everything
+ * that assumes a property checks its flag (a tensor that fails one runs the general kernel, or the entry point raises).
+ * Grid-aligned orthotropic tensors on box voxels set every flag; a rotated (fully anisotropic) tensor sets none. */
+enum {
+    VFEM_PATH_MODE_SPACE    = 1,  /* the 45-entry mode-space pattern: LDS-DMA / register-staged apply and residual, plane-range apply; else k_apply_gather */
+    VFEM_PATH_GS_RESIDENT   = 2,  /* the 36 magnitudes of the resident level-0 sweeps (VFEM_OPT_GS_RESIDENT is ignored without it); else the coefficient table */
+    VFEM_PATH_K0_MIRROR     = 4,  /* K0 commutes with the axis reflections: marching level-0 sweep, plane-range sweeps; else the row kernels */
+    VFEM_PATH_L1_MIRROR     = 8,  /* vfem_mg_tensor_paths: the coarsened matrices are mirror images: level 1 per mirror class (VFEM_OPT_L1_MERGED, _L1_DIAG,
+                                     _L1_SPLIT); else per incident element with all eight matrices */
+    VFEM_PATH_Q2_MODE_SPACE = 16  /* vfem_gsim_tensor_paths, degree-2 hexahedra: block-diagonal mode-space K0 (marching / pencil apply); else the dense gather apply */
+};
+int vfem_sim_tensor_paths(const vfem_sim *sim);
 /* E_0 / E_min / gamma properties (VoxelFEM.cc:77-79; TPS.hh:1170-1175) */
 int vfem_sim_set_simp(vfem_sim *sim, double E0, double Emin, double gamma);
 /* fullDensityElementStiffnessMatrix (TPS.hh:755): 24x24 doubles, row-major, to HOST */
@@ -166,6 +186,7 @@ int vfem_mg_level_dims(const vfem_mg *mg, int level, int64_t nelems_host[3]);
 int64_t vfem_mg_level_num_nodes(const vfem_mg *mg, int level);
 int vfem_mg_level_dirichlet_mask(const vfem_mg *mg, int level, uint8_t *mask_host);  /* coarsened masks, MG.hh:57-84 */
 int vfem_mg_set_symmetric_gauss_seidel(vfem_mg *mg, int symmetric);                  /* MG.hh:92-94 */
+int vfem_mg_tensor_paths(const vfem_mg *mg);          /* vfem_sim_tensor_paths of the simulator | VFEM_PATH_L1_MIRROR of this hierarchy */
 /* debug_get_x / debug_get_b (MG.hh:734-735) and the PCG residual handed to it_callback (MG.hh:726-729):
  * device pointer of an internal field; which = 0: m_x[level], 1: m_b[level], 2: PCG residual r (level ignored). */
 const double *vfem_mg_field_ptr(const vfem_mg *mg, int which, int level);
@@ -301,6 +322,10 @@ int64_t vfem_gsim_num_nodes(const vfem_gsim *sim);
 int64_t vfem_gsim_num_elements(const vfem_gsim *sim);
 int vfem_gsim_ke_size(const vfem_gsim *sim);                       /* N * (p+1)^N */
 int vfem_gsim_set_isotropic(vfem_gsim *sim, double young, double poisson);
+/* vfem_sim_set_elasticity_tensor for the generic path: D is n x n row-major, n = 6 in 3-D (xx yy zz yz xz xy) and n = 3 in 2-D
+ * (xx yy xy; a plane-stress material arrives already reduced).  K0 is integrated by the same Gauss loop as the isotropic one. */
+int vfem_gsim_set_elasticity_tensor(vfem_gsim *sim, const double *D_host, int n);
+int vfem_gsim_tensor_paths(const vfem_gsim *sim);     /* VFEM_PATH_Q2_MODE_SPACE or 0 */
 int vfem_gsim_set_simp(vfem_gsim *sim, double E0, double Emin, double gamma);
 int vfem_gsim_k0(const vfem_gsim *sim, double *K0_host);           /* ke x ke row-major */
 int vfem_gsim_set_dirichlet(vfem_gsim *sim, const uint8_t *mask_host, const double *values_host);

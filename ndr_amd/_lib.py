@@ -44,6 +44,8 @@ SIGNATURES = {
     "vfem_sim_num_nodes": (c_int64, [c_void_p]),
     "vfem_sim_num_elements": (c_int64, [c_void_p]),
     "vfem_sim_set_isotropic": (c_int, [c_void_p, c_double, c_double]),
+    "vfem_sim_set_elasticity_tensor": (c_int, [c_void_p, c_void_p]),
+    "vfem_sim_tensor_paths": (c_int, [c_void_p]),
     "vfem_sim_set_simp": (c_int, [c_void_p, c_double, c_double, c_double]),
     "vfem_sim_set_option": (c_int, [c_void_p, c_int, c_int]),
     "vfem_sim_k0": (c_int, [c_void_p, c_void_p]),
@@ -72,6 +74,7 @@ SIGNATURES = {
     "vfem_mg_level_num_nodes": (c_int64, [c_void_p, c_int]),
     "vfem_mg_level_dirichlet_mask": (c_int, [c_void_p, c_int, c_void_p]),
     "vfem_mg_set_symmetric_gauss_seidel": (c_int, [c_void_p, c_int]),
+    "vfem_mg_tensor_paths": (c_int, [c_void_p]),
     "vfem_mg_field_ptr": (c_void_p, [c_void_p, c_int, c_int]),
     "vfem_mg_update_operators": (c_int, [c_void_p, c_void_p]),
     "vfem_mg_export_level_ke": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p]),
@@ -123,6 +126,8 @@ SIGNATURES = {
     "vfem_gsim_num_elements": (c_int64, [c_void_p]),
     "vfem_gsim_ke_size": (c_int, [c_void_p]),
     "vfem_gsim_set_isotropic": (c_int, [c_void_p, c_double, c_double]),
+    "vfem_gsim_set_elasticity_tensor": (c_int, [c_void_p, c_void_p, c_int]),
+    "vfem_gsim_tensor_paths": (c_int, [c_void_p]),
     "vfem_gsim_set_simp": (c_int, [c_void_p, c_double, c_double, c_double]),
     "vfem_gsim_k0": (c_int, [c_void_p, c_void_p]),
     "vfem_gsim_set_dirichlet": (c_int, [c_void_p, c_void_p, c_void_p]),

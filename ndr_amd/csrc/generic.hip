@@ -615,6 +615,9 @@ struct vfem_gsim {
     GDims d;
     double h[3] = {1, 1, 1};
     double lambda = 0.0, mu = 0.5;                 // ETensor(1, 0), TPS.hh:1379
+    bool general_tensor = false;                   // K0 comes from D (vfem_gsim_set_elasticity_tensor) instead of (lambda, mu)
+    double D[36];                                  // flattened tensor, nf x nf row-major (nf = 3: xx yy xy; 6: xx yy zz yz xz xy)
+    long long material_version = 0;                // bumped by update_k0: hierarchies rebuild their coarsened reference matrices
     double E0 = 1.0, Emin = 1e-9, gamma = 3.0;     // TPS.hh:1392-1394
     std::vector<double> K0;
     DevBuf<double> dK0, rho, E, dvals;
@@ -669,6 +672,7 @@ struct vfem_gmg {
     DevBuf<double> tr1, tr2;           // intermediates of the axis-by-axis transfers
     DevBuf<double> c2tab;              // degree-2 hexahedra: c2K0[g][f] = I_g^T cK0[f] I_g as [entry][64] (level 2 straight from the moduli)
     DevBuf<double> l1tab;              // degree-2 hexahedra: cK0 regrouped for k_q2_level1, [ln][m][f][r][c]
+    long long material_version = -1;   // fine->material_version the tables derived from K0 (cK0, l1tab, c2tab) were built for
     CoarsestSolver coarsest;           // exact solve of level L: always the dense inverse here (mode auto = dense)
 };
 
@@ -700,6 +704,10 @@ void vfem_gsim::update_k0() {
     int nq = 1;
     for (int a = 0; a < N; ++a) nq *= q1;
     std::vector<double> G((size_t) npe * 3);
+    // a general tensor: C_apbq = D[flat(a,p)][flat(b,q)] (Flattening.hh); the isotropic case keeps its own three-term form
+    static const int flat3[3][3] = {{0, 5, 4}, {5, 1, 3}, {4, 3, 2}}, flat2[3][3] = {{0, 2, 0}, {2, 1, 0}, {0, 0, 0}};
+    const int (*flat)[3] = N == 3 ? flat3 : flat2;
+    const int nf = N == 3 ? 6 : 3;
     for (int qi = 0; qi < nq; ++qi) {
         int qa[3] = {0, 0, 0};
         { int m = qi; for (int a = N - 1; a >= 0; --a) { qa[a] = m % q1; m /= q1; } }
@@ -719,11 +727,22 @@ void vfem_gsim::update_k0() {
                 double dot = 0.0;
                 for (int dd = 0; dd < N; ++dd) dot += G[3 * n + dd] * G[3 * m + dd];
                 for (int a = 0; a < N; ++a)
-                    for (int b = 0; b < N; ++b)
+                    for (int b = 0; b < N; ++b) {
+                        if (general_tensor) {
+                            double v = 0.0;
+                            for (int pp = 0; pp < N; ++pp)
+                                for (int qq = 0; qq < N; ++qq) v += D[flat[a][pp] * nf + flat[b][qq]] * G[3 * n + pp] * G[3 * m + qq];
+                            K0[(size_t) (N * n + a) * ke + N * m + b] += w * v;
+                        } else
                         K0[(size_t) (N * n + a) * ke + N * m + b] +=
                             w * (lambda * G[3 * n + a] * G[3 * m + b] + mu * G[3 * n + b] * G[3 * m + a] + (a == b ? mu * dot : 0.0));
+                    }
             }
     }
+    if (general_tensor)                            // symmetric bit for bit, like the isotropic sum (the order of the terms differs across the diagonal)
+        for (int i = 0; i < ke; ++i)
+            for (int j = 0; j < i; ++j) K0[(size_t) i * ke + j] = K0[(size_t) j * ke + i];
+    ++material_version;
     dK0.alloc(K0.size());
     VFEM_HIP(hipMemcpy(dK0.p, K0.data(), K0.size() * sizeof(double), hipMemcpyHostToDevice));
     q2_fast = false;
@@ -918,9 +937,14 @@ static void coarsen_through_virtual_level1(vfem_gmg *mg, long long first2, long 
     VFEM_HIP(hipGetLastError());
 }
 
+static void gmg_setup_transfer_tables(vfem_gmg *mg);
 static void gmg_update(vfem_gmg *mg, hipStream_t s) {
     vfem_gsim *sim = mg->fine;
     const int N = sim->d.N;
+    if (mg->material_version != sim->material_version) {       // the material changed since the hierarchy was created
+        VFEM_HIP(hipStreamSynchronize(s));
+        gmg_setup_transfer_tables(mg);
+    }
     if (mg->first_active > 0 && mg->external_ke_level != mg->first_active)
         throw Error("the element matrices of the first active level have not been imported (vfem_gmg_import_level_ke)");
     const int l_first = mg->first_active > 0 ? mg->first_active + 1 : 1;
@@ -1080,10 +1104,24 @@ int vfem_gsim_set_isotropic(vfem_gsim *sim, double young, double poisson) {
     sim->lambda = sim->d.N == 2 ? poisson * young / (1.0 - poisson * poisson)
                                 : poisson * young / ((1.0 + poisson) * (1.0 - 2.0 * poisson));
     sim->mu = young / (2.0 + 2.0 * poisson);
+    sim->general_tensor = false;
     sim->update_k0();
     ++sim->operator_version;
     VFEM_CATCH
 }
+int vfem_gsim_set_elasticity_tensor(vfem_gsim *sim, const double *D, int n) {
+    VFEM_TRY
+    if (n != (sim->d.N == 3 ? 6 : 3)) throw Error("the flattened tensor of a " + std::to_string(sim->d.N) + "-D simulator is " +
+                                                  (sim->d.N == 3 ? "6 x 6" : "3 x 3"));
+    check_flattened_tensor(D, n);
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) sim->D[i * n + j] = 0.5 * (D[i * n + j] + D[j * n + i]);
+    sim->general_tensor = true;
+    sim->update_k0();
+    ++sim->operator_version;
+    VFEM_CATCH
+}
+int vfem_gsim_tensor_paths(const vfem_gsim *sim) { return sim->q2_fast ? VFEM_PATH_Q2_MODE_SPACE : 0; }
 int vfem_gsim_set_simp(vfem_gsim *sim, double E0, double Emin, double gamma) {
     VFEM_TRY
     sim->E0 = E0; sim->Emin = Emin; sim->gamma = gamma;
@@ -1216,6 +1254,7 @@ static void gmg_setup_transfer_tables(vfem_gmg *mg) {
     mg->phi.alloc(phi.size()); mg->cK0.alloc(cK0.size());
     VFEM_HIP(hipMemcpy(mg->phi.p, phi.data(), phi.size() * sizeof(double), hipMemcpyHostToDevice));
     VFEM_HIP(hipMemcpy(mg->cK0.p, cK0.data(), cK0.size() * sizeof(double), hipMemcpyHostToDevice));
+    mg->material_version = fine->material_version;
 }
 static void gmg_alloc_level_fields(GLevel &lv) {
     lv.mask.alloc((size_t) lv.d.nnodes);

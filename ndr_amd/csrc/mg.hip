@@ -226,6 +226,8 @@ static void factor_coarsest(vfem_mg *mg, hipStream_t s) {
     VFEM_HIP(hipStreamSynchronize(s));   // tmpS lifetime
 }
 
+static void build_reference_tables(vfem_mg *mg);
+
 void vfem::update_operators(vfem_mg *mg, hipStream_t s) {
     vfem_sim *sim = mg->fine;
     // the reference rebuilds the coarse operators at the start of every solve (MG.hh:690-691) because its densities may have
@@ -233,6 +235,10 @@ void vfem::update_operators(vfem_mg *mg, hipStream_t s) {
     // constructor solve followed by setVars with the same design) keeps Galerkin matrices, stencils and the dense inverse
     if (mg->operators_valid && mg->operators_version == sim->operator_version) return;
     ScopedTimer tm("updateElementStiffnessMatrices");
+    if (mg->material_version != sim->material_version) {     // the material changed since the hierarchy was created
+        VFEM_HIP(hipStreamSynchronize(s));
+        build_reference_tables(mg);
+    }
     const int L = mg->slab ? mg->L - 1 : mg->L;      // the last level of a slab hierarchy only serves the grid transfers
     // Galerkin element matrices for levels >= 2 (level 1 stays virtual: sum_f E_f cK0[f])
     // (element arrays cover lv.da = node grid + extra x-layers; array origins halve exactly from level to level)
@@ -326,7 +332,8 @@ void vfem::cycle_from_level(vfem_mg *mg, int l, int nsmooth, bool fmg, hipStream
     mg_cycle::cycles(o, l, 1, nsmooth, true, fmg);
 }
 
-static void finish_mg_create(vfem_mg *mg) {
+// what the hierarchy derives from the simulator's reference matrix K0 alone; rebuilt when the material changes (update_operators)
+static void build_reference_tables(vfem_mg *mg) {
     vfem_sim *fine = mg->fine;
     // interpolation of a coarse element onto its child g = 4gx+2gy+gz: phi[g](fine node, coarse node), nodes numbered x slowest
     double phi[8][64];
@@ -363,6 +370,12 @@ static void finish_mg_create(vfem_mg *mg) {
         mg->l1mtab.alloc(L1M_TABLE_DOUBLES);
         VFEM_HIP(hipMemcpy(mg->l1mtab.p, mt, sizeof(mt), hipMemcpyHostToDevice));
     }
+    mg->material_version = fine->material_version;
+}
+
+static void finish_mg_create(vfem_mg *mg) {
+    vfem_sim *fine = mg->fine;
+    build_reference_tables(mg);
     for (int l = mg->first_active; l <= mg->L; ++l) {
         MgLevel &lv = mg->lv[(size_t) l];
         lv.x.alloc((size_t) lv.d.nn * 3); lv.b.alloc((size_t) lv.d.nn * 3); lv.r.alloc((size_t) lv.d.nn * 3);
@@ -428,6 +441,9 @@ int vfem_mg_create_slab(vfem_mg **out, vfem_sim *fine, int n_levels, const vfem_
                         const uint8_t *const *masks_host) {
     VFEM_TRY
     if (n_levels < 1) throw Error("need at least one level");
+    if (!fine->fast_ok || !fine->k0_mirror_ok)
+        throw Error("slab hierarchies need a material on the mode-space kernels (isotropic or grid-aligned orthotropic tensor): "
+                    "the plane-range apply has no general form");
     std::unique_ptr<vfem_mg> mg(new vfem_mg);
     mg->fine = fine; mg->L = n_levels - 1; mg->slab = true;
     mg->lv.resize((size_t) n_levels);
@@ -479,6 +495,10 @@ int vfem_mg_level_dirichlet_mask(const vfem_mg *mg, int level, uint8_t *mask_hos
     VFEM_CATCH
 }
 int vfem_mg_set_symmetric_gauss_seidel(vfem_mg *mg, int symmetric) { mg->symmetric_gs = symmetric != 0; return 0; }
+int vfem_mg_tensor_paths(const vfem_mg *mg) {
+    // (the level-1 flag is that of the reference matrices the hierarchy currently holds: they follow the material at the next update)
+    return vfem_sim_tensor_paths(mg->fine) | (mg->mf1_sym ? VFEM_PATH_L1_MIRROR : 0);
+}
 const double *vfem_mg_field_ptr(const vfem_mg *mg, int which, int level) {
     if (which == 2) return mg->lv[0].b.p;          // the PCG residual lives in the level-0 right-hand side
     if (level < 0 || level > mg->L) return nullptr;

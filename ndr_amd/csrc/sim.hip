@@ -10,7 +10,7 @@
 using namespace vfem;
 
 // ------------------------------------------------------------------------------------------
-// reference element: closed-form Q1 stiffness for an axis-aligned box voxel with isotropic C.
+// reference element: closed-form Q1 stiffness for an axis-aligned box voxel, isotropic C or any flattened tensor D.
 // Same quantity as Element_T::Stiffness (TPS.hh:127-140), which integrates it by 2-point Gauss
 // quadrature (exact for these integrands); derived here from the 1-D integrals
 //   Mm[a][b] = int N_a N_b,  Dd[a][b] = int N_a' N_b',  Gg[a][b] = int N_a' N_b   on [0,1].
@@ -31,14 +31,27 @@ void vfem_sim::update_k0() {
         }
         return v;
     };
+    // a general tensor: K0[(n,a),(m,b)] = vol sum_pq C_apbq int d_p N_n d_q N_m with C_apbq = D[flat(a,p)][flat(b,q)].  The isotropic
+    // case keeps its own three-term form (the same sum with the zero terms left out: results of existing inputs stay bit-identical)
+    static const int flat[3][3] = {{0, 5, 4}, {5, 1, 3}, {4, 3, 2}};              // Flattening.hh: xx yy zz yz xz xy
     for (int n = 0; n < 8; ++n)
         for (int a = 0; a < 3; ++a)
             for (int m = 0; m < 8; ++m)
                 for (int b = 0; b < 3; ++b) {
-                    double v = lambda * I(n, m, a, b) + mu * I(n, m, b, a);
-                    if (a == b) v += mu * (I(n, m, 0, 0) + I(n, m, 1, 1) + I(n, m, 2, 2));
+                    double v = 0.0;
+                    if (general_tensor) {
+                        // (one of each transposed pair is summed, the other copies it: K0 is symmetric bit for bit whatever the order of the terms)
+                        const bool tr = a > b || (a == b && n > m);
+                        const int n_ = tr ? m : n, a_ = tr ? b : a, m_ = tr ? n : m, b_ = tr ? a : b;
+                        for (int p = 0; p < 3; ++p)
+                            for (int q = 0; q < 3; ++q) v += D[flat[a_][p] * 6 + flat[b_][q]] * I(n_, m_, p, q);
+                    } else {
+                        v = lambda * I(n, m, a, b) + mu * I(n, m, b, a);
+                        if (a == b) v += mu * (I(n, m, 0, 0) + I(n, m, 1, 1) + I(n, m, 2, 2));
+                    }
                     K0[(3 * n + a) * 24 + 3 * m + b] = vol * v;
                 }
+    ++material_version;
     // mode-space form: Dmode = T K0 T^T / 64 with T = H (x) H (x) H, H = [[1,1],[-1,1]] per axis.
     // For a box voxel with an orthotropic/isotropic tensor only 45 entries survive:
     // 21 diagonal ones (the three rigid translations are null) and 12 symmetric couplings.
@@ -121,7 +134,20 @@ void vfem_sim::update_k0() {
     VFEM_HIP(hipMemcpy(dGsTab.p, tab, sizeof(tab), hipMemcpyHostToDevice));
 }
 
-double vfem::compliance(long long n, const double *f, const double *u, hipStream_t s) {
+void vfem::check_flattened_tensor(const double *D, int n) {
+    double maxabs = 0.0;
+    for (int q = 0; q < n * n; ++q) {
+        if (!std::isfinite(D[q])) throw Error("elasticity tensor has a non-finite entry");
+        maxabs = std::max(maxabs, std::fabs(D[q]));
+    }
+    for (int i = 0; i < n; ++i) {
+        if (!(D[i * n + i] > 0.0)) throw Error("elasticity tensor is not positive definite");
+        for (int j = 0; j < i; ++j)
+            if (std::fabs(D[i * n + j] - D[j * n + i]) > 1e-10 * maxabs) throw Error("elasticity tensor is not symmetric");
+    }
+}
+
+double vfem::compliance(long long n,const double *f, const double *u, hipStream_t s) {
     double *tmp = nullptr;                           // the partial sums, then the result
     VFEM_HIP(hipMallocAsync((void **) &tmp, (REDUCE_SCRATCH_DOUBLES + 1) * sizeof(double), s));
     launch_dot(n, f, u, tmp, tmp + REDUCE_SCRATCH_DOUBLES, s);
@@ -172,9 +198,24 @@ int vfem_sim_set_isotropic(vfem_sim *sim, double young, double poisson) {
     VFEM_TRY
     sim->lambda = poisson * young / ((1.0 + poisson) * (1.0 - 2.0 * poisson));   // ElasticityTensor.hh:105-106
     sim->mu = young / (2.0 + 2.0 * poisson);
+    sim->general_tensor = false;
     sim->update_k0();
     ++sim->operator_version;
     VFEM_CATCH
+}
+int vfem_sim_set_elasticity_tensor(vfem_sim *sim, const double D[36]) {
+    VFEM_TRY
+    check_flattened_tensor(D, 6);
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) sim->D[i * 6 + j] = 0.5 * (D[i * 6 + j] + D[j * 6 + i]);
+    sim->general_tensor = true;
+    sim->update_k0();
+    ++sim->operator_version;
+    VFEM_CATCH
+}
+int vfem_sim_tensor_paths(const vfem_sim *sim) {
+    return (sim->fast_ok ? VFEM_PATH_MODE_SPACE : 0) | (sim->gs_resident_ok ? VFEM_PATH_GS_RESIDENT : 0) |
+           (sim->k0_mirror_ok ? VFEM_PATH_K0_MIRROR : 0);
 }
 int vfem_sim_set_simp(vfem_sim *sim, double E0, double Emin, double gamma) {
     VFEM_TRY
@@ -273,7 +314,7 @@ int vfem_sim_apply_k_planes(const vfem_sim *sim, const double *u, double *out, i
     VFEM_TRY
     if (plane_lo < 0 || plane_hi > sim->d.NX - 1) throw Error("plane range outside the node grid");
     if (plane_lo > plane_hi) return 0;
-    if (!sim->fast_ok) throw Error("plane-range apply needs the mode-space kernel (box voxels, isotropic tensor)");
+    if (!sim->fast_ok) throw Error("plane-range apply needs the mode-space kernel (box voxels, isotropic or grid-aligned orthotropic tensor)");
     if (!launch_apply_dma(sim->d, sim->Dm, sim->Ep(), sim->E.p + sim->n_store(), u, out, S(stream), (int) plane_lo, (int) plane_hi,
                           sim->tune.dma_chunks, sim->tune.dma_strip, nullptr, nullptr, sim->tune.dma_lx))
         throw Error("plane-range apply needs 8-byte aligned device buffers");

@@ -33,6 +33,11 @@ constexpr size_t REDUCE_SCRATCH_DOUBLES = 2048;
 // is stream-ordered (hipMallocAsync does not synchronise the device): evaluations on different streams share no partial sums.
 double compliance(long long n, const double *f, const double *u, hipStream_t s);
 
+// what the set_elasticity_tensor entry points refuse before anything is rebuilt (sim.hip): an n x n flattened tensor that is not
+// finite, not symmetric (1e-10 of its largest entry, the bound of the material files) or has a non-positive diagonal entry.
+// (Positive definiteness is checked by the host class that parses materials; this is the C boundary's own sanity check.)
+void check_flattened_tensor(const double *D, int n);
+
 // Galerkin projection out = Phi^T K Phi of an element matrix (MG.hh:644-648; mg.hip): K, scratch, out are ke x ke with ke = N * npe
 // (node-major dofs), Phi(fine node, coarse node) is npe x npe and acts on every component alike.  T = K Phi, then Phi^T T, each
 // entry summed over the node index ascending from 0.0.

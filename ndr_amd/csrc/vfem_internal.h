@@ -311,6 +311,9 @@ struct vfem_sim {
     vfem::Dims d;
     double h[3];
     double lambda = 0.0, mu = 0.5;              // ETensor(1, 0) default, TPS.hh:1379
+    bool   general_tensor = false;              // K0 comes from D (vfem_sim_set_elasticity_tensor) instead of (lambda, mu)
+    double D[36];                               // flattened tensor, order xx yy zz yz xz xy, tensor components (no factor 2)
+    long long material_version = 0;             // bumped by update_k0: hierarchies rebuild their coarsened reference matrices
     double E0 = 1.0, Emin = 1e-9, gamma = 3.0;  // TPS.hh:1392-1394
     double K0[576];                             // host copy, row-major
     double Dm[64];                              // symmetry-reduced (mode-space) coefficients, host
@@ -370,6 +373,7 @@ struct vfem_mg {
     bool operators_valid = false;
     long long operators_version = 0;            // fine->operator_version the coarse operators were built for
     bool mf1_sym = false;                       // cK0[f] are mirror images of cK0[0]: level-1 sweeps read cK0[0] only
+    long long material_version = -1;            // fine->material_version the coarsened reference matrices were built for
     vfem::CoarsestSolver coarsest;              // exact solve of level L (not in a slab hierarchy)
 };
 

@@ -120,14 +120,29 @@ class HaloExchanger:
         return self.comm.all_reduce(s) if p.world > 1 else s
 
 
+# VFEM_PATH_* of include/vfem.h that a slab decomposition needs of its material: the plane-range apply and the plane-range sweeps
+# exist in the mode-space / mirror form only (degree 1), the degree-2 slabs run the marching apply
+SLAB_PATHS_TRILINEAR, SLAB_PATHS_Q2 = 1 | 4, 16
+
+
+def require_slab_material(sim, needed):
+    """refuse, at construction, a material whose K0 lacks the structure the slab kernels assume"""
+    if sim._tensor_paths() & needed != needed:
+        raise RuntimeError("slab decomposition supports isotropic and grid-aligned orthotropic materials only: this elasticity "
+                           "tensor does not have the mirror symmetry the plane-range kernels need (an anisotropic material runs "
+                           "on a single device)")
+
+
 class HipLocalOps:
     """Per-rank operator: the libvfem simulator of the local slab (owned + ghost layers)."""
 
-    def __init__(self, part, bbmin, bbmax, young=1.0, poisson=0.3, E0=1.0, Emin=1e-4, gamma=3.0):
+    def __init__(self, part, bbmin, bbmax, young=1.0, poisson=0.3, E0=1.0, Emin=1e-4, gamma=3.0, tensor=None):
+        """``tensor``: an ``ElasticityTensor`` instead of (young, poisson); it must run on the mode-space kernels"""
         from . import pyVoxelFEM as pv
         lo, hi = part.local_bbox(bbmin, bbmax)
         self.tps = pv.TensorProductSimulator1_1_1([lo, hi], list(part.local_ne))
-        _lib.check(self.tps._c("set_isotropic")(self.tps._h, young, poisson))
+        self.tps.ETensor = tensor if tensor is not None else pv.ElasticityTensor(young, poisson)
+        require_slab_material(self.tps, SLAB_PATHS_TRILINEAR)
         self.tps.E_0, self.tps.E_min, self.tps.gamma = E0, Emin, gamma
         self.device = torch.device("cuda", torch.cuda.current_device())
 
@@ -428,8 +443,13 @@ class DistributedMGSolver:
 
         # the replicated simulator + hierarchy (coarse cycles), the local slab simulator (node grid: owned + ghost layers; element
         # arrays padded) and the Dirichlet masks of the local grids
+        from .materials import ElasticityTensor, read_material
+        # parsed once; every rank simulator receives the tensor itself (material_path may also be an ElasticityTensor)
+        tensor = material_path if isinstance(material_path, ElasticityTensor) else read_material(material_path, 3)
+
         def material(sim):
-            sim.readMaterial(material_path)
+            sim.ETensor = tensor
+            require_slab_material(sim, self.SLAB_PATHS)
             sim.E_0, sim.E_min, sim.gamma = E0, Emin, gamma
             return sim
         bbmin, bbmax = np.asarray(bbmin, float), np.asarray(bbmax, float)
@@ -489,6 +509,7 @@ class DistributedMGSolver:
 
     # ---- small helpers -------------------------------------------------------------------
     DEGREE, GHOST = 1, 1           # polynomial degree; ghost element layers per neighbour
+    SLAB_PATHS = SLAB_PATHS_TRILINEAR
     MIN_LAYERS = 8                 # owned element layers per rank on the deepest distributed level (automatic choice)
     MAX_AUTO_DIST_LEVELS = None    # no cap on the automatic choice
     _MG_PREFIX = "vfem_mg_"        # C entry points of the hierarchy handles (the degree-2 subclass uses vfem_gmg_)

@@ -24,7 +24,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from .distributed import DistributedMGSolver, LevelGeom
+from .distributed import SLAB_PATHS_Q2, DistributedMGSolver, LevelGeom
 from .slab_comm import MAX
 
 P = 2            # polynomial degree
@@ -146,6 +146,7 @@ class DistributedMGSolverQ2(DistributedMGSolver):
     and memory are the real rank's)."""
 
     DEGREE, GHOST = P, G
+    SLAB_PATHS = SLAB_PATHS_Q2
     C_DRIVER_AVAILABLE = False     # the degree-2 cycle (27 colours in three groups, four-plane halos) is driven from Python
     _MG_PREFIX = "vfem_gmg_"
     KE_DOUBLES = 81 * 81

@@ -26,14 +26,17 @@ import torch
 
 from . import _lib
 from . import band as _band
+from . import materials as _materials
 
 __all__ = [
     "TensorProductSimulator", "TopologyOptimizationProblem", "ComplianceObjective",
     "MultigridComplianceObjective", "OCOptimizer", "PythonFilter", "ProjectionFilter",
     "SmoothingFilter", "LangelaarFilter", "applyFilter", "TotalVolumeConstraint",
     "benchmark_reset", "benchmark_report", "benchmark_start_timer_section",
-    "benchmark_stop_timer_section", "benchmark_start_timer", "benchmark_stop_timer", "detail",
+    "benchmark_stop_timer_section", "benchmark_start_timer", "benchmark_stop_timer", "detail", "ElasticityTensor",
 ]
+
+ElasticityTensor = _materials.ElasticityTensor       # what sim.ETensor returns and takes (MeshFEM binds it in its own `tensors` module)
 
 
 def _stream():
@@ -70,6 +73,8 @@ def _to_np(t):
 # ----------------------------------------------------------------------------------------------
 
 def _read_isotropic_material(path):
+    """(young, poisson) of an isotropic material file: what the isotropic oracles of the tests are built from; the simulators read
+    materials of every type through ``materials.read_material``"""
     with open(path) as fh:
         m = json.load(fh)
     if m.get("type", "isotropic_material") != "isotropic_material":
@@ -172,6 +177,12 @@ def _constant_strain_load(eps, lam, mu, h, degree, rho_grid):
     N = len(h)
     eps = np.asarray(eps, dtype=np.float64).reshape(N, N)
     sigma = lam * np.trace(eps) * np.eye(N) + 2.0 * mu * 0.5 * (eps + eps.T)            # isotropic C : eps
+    return _stress_load(sigma, h, degree, rho_grid)
+
+
+def _stress_load(sigma, h, degree, rho_grid):
+    """the nodal load of the constant stress ``sigma`` = C : eps (any tensor C), see ``_constant_strain_load``"""
+    N = len(h)
     I = {1: np.array([0.5, 0.5]), 2: np.array([1.0, 4.0, 1.0]) / 6.0}[degree]
     dI = {1: np.array([-1.0, 1.0]), 2: np.array([-1.0, 0.0, 1.0])}[degree]
     vol = float(np.prod(h))
@@ -584,19 +595,48 @@ class _Simulator:
 
     # ---- material / SIMP ----
     def readMaterial(self, materialPath):
-        young, poisson = _read_isotropic_material(materialPath)
-        self._young, self._poisson = young, poisson
-        _lib.check(self._c("set_isotropic")(self._h, young, poisson))
+        """TPS::readMaterial (TPS.hh:326-331): isotropic, orthotropic and symmetric / anisotropic material files"""
+        self._set_etensor(_materials.read_material(materialPath, self.N))
+
+    # ``sim.ETensor`` (TPS.hh:333-339) reads and assigns an ``ElasticityTensor``.  It is resolved per instance (the tuned class also
+    # names it as a property): the public names of the classes themselves stay those a test pins.
+    def __getattr__(self, name):              # (only reached for names that are neither set on the instance nor defined by the class)
+        if name == "ETensor":
+            return self._get_etensor()
+        raise AttributeError(name)
+
+    def __setattr__(self, name, value):
+        if name == "ETensor":
+            self._set_etensor(value)
+        else:
+            object.__setattr__(self, name, value)
+
+    def _get_etensor(self):
+        t = self.__dict__.get("_etensor")
+        if t is None:
+            return _materials.ElasticityTensor(1.0, 0.0, dim=self.N)           # ETensor(1, 0) default, TPS.hh:1379
+        return _materials.ElasticityTensor(t, dim=self.N)                      # a copy: assigning to ETensor is what changes the simulator
+
+    def _set_etensor(self, tensor):
+        if not isinstance(tensor, _materials.ElasticityTensor):
+            raise TypeError("ETensor takes an ndr_amd.ElasticityTensor")
+        if tensor.dim != self.N:
+            raise RuntimeError("Dimension mismatch: %d vs %d" % (tensor.dim, self.N))
+        _materials.require_positive_definite(tensor)
+        t = _materials.ElasticityTensor(tensor, dim=self.N)
+        if t._iso is not None:                    # the isotropic entry point keeps its arithmetic: existing results stay bit-identical
+            _lib.check(self._c("set_isotropic")(self._h, t._iso[0], t._iso[1]))
+        else:
+            self._push_tensor(np.ascontiguousarray(t._D))
+        self._etensor = t
         self._direct_mg = None                    # the reference resets its solver when the operator changes (TPS.hh:404)
+
+    def _tensor_paths(self):
+        """the VFEM_PATH_* bits of include/vfem.h: which tuned kernels the current material runs on"""
+        return int(self._c("tensor_paths")(self._h))
 
     def _push_simp(self):
         _lib.check(self._c("set_simp")(self._h, self._E0, self._Emin, self._gamma))
-
-    def _lame(self):
-        """ElasticityTensor::setIsotropic (ElasticityTensor.hh:100-133): 3-D Lame parameters, plane stress in 2-D"""
-        E, nu = getattr(self, "_young", 1.0), getattr(self, "_poisson", 0.0)         # ETensor(1, 0) default, TPS.hh:1379
-        lam = nu * E / ((1.0 + nu) * (1.0 - 2.0 * nu)) if self.N == 3 else nu * E / (1.0 - nu * nu)
-        return lam, E / (2.0 + 2.0 * nu)
 
     def readDensities(self, materialPath, fieldName="density"):
         """TPS::readDensities (VoxelFEM.cc:54)"""
@@ -604,9 +644,9 @@ class _Simulator:
 
     def constantStrainLoad(self, eps):
         """TPS::constantStrainLoad (VoxelFEM.cc:66), evaluated on the device"""
-        lam, mu = self._lame()
+        sigma = self._get_etensor().doubleContract(eps)                       # C : eps with the actual tensor
         rho = self.getDensities_device()[:self.numElements()].reshape(tuple(int(n) for n in self._ne))
-        return _to_np(_constant_strain_load(eps, lam, mu, (self._bbmax - self._bbmin) / self._ne, self.P, rho))
+        return _to_np(_stress_load(sigma, (self._bbmax - self._bbmin) / self._ne, self.P, rho))
 
     @property
     def _GETK_MAX_ELEMENTS(self):
@@ -851,9 +891,10 @@ class TensorProductSimulator1_1_1(_Simulator):
     def _create(self, out, lo, hi, ne, pad_lo, pad_hi):
         return self._c("create_padded")(out, lo, hi, ne, pad_lo, pad_hi)
 
-    @property
-    def ETensor(self):
-        raise RuntimeError("ETensor objects are not exposed; use readMaterial (isotropic materials)")
+    ETensor = property(_Simulator._get_etensor, _Simulator._set_etensor)
+
+    def _push_tensor(self, D):
+        _lib.check(self._c("set_elasticity_tensor")(self._h, D.ctypes.data_as(ctypes.c_void_p)))
 
     def setUniformDensities(self, density):
         # filled by the library: no temporary (1 GiB at 512^3); it raises the same range error
@@ -891,6 +932,9 @@ class _GenericSimulator(_Simulator):
 
     def _create(self, out, lo, hi, ne, pad_lo, pad_hi):
         return self._c("create_padded")(out, self.N, self.P, lo, hi, ne, pad_lo, pad_hi)
+
+    def _push_tensor(self, D):
+        _lib.check(self._c("set_elasticity_tensor")(self._h, D.ctypes.data_as(ctypes.c_void_p), int(D.shape[0])))
 
     def _stand_in_solve(self, mg, f):
         # a grid with odd element counts cannot be coarsened; beyond the dense-factorisation size it is solved by plain CG
