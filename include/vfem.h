@@ -456,6 +456,35 @@ int vfem_mlp_backward_grid_range(vfem_mlp *mlp, const int64_t n_host[3], const d
 int vfem_adam_step(int64_t n, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, float lr, float beta1,
                    float beta2, float eps, int step, void *stream);
 
+/* ---- periodic homogenisation of a voxel cell (TPPeriodicHomogenization.hh; DESIGN "Periodic homogenisation") ----
+ * Handle-free, degree-1 elements, dim = 2 or 3.  Every entry point takes the cell and its element constants:
+ *   nelems_host[dim]   elements per axis (>= 2 each); periodic node (i_0, .., i_{dim-1}), last axis fastest, is the unknown of every
+ *                      grid node congruent to it modulo nelems, so there are prod(nelems) periodic nodes; node 0 is pinned (w = 0)
+ *   K0_host [ke][ke]   full-density element matrix, ke = dim 2^dim, local nodes with the last axis fastest, dof = dim node + component
+ *   L_host  [ke][S]    L[:, q] = element load of the constant stress C : e_q, S = 3 (xx yy xy) or 6 (xx yy zz yz xz xy), e_q with
+ *                      0.5 on both off-diagonal entries of a shear case
+ *   D_host  [S][S]     flattened tensor (row q = C : e_q), vol = voxel volume
+ *   E (device) [prod(nelems)]  element moduli E_min + rho^gamma (E_0 - E_min), last axis fastest
+ * W (device) is [S][periodic nodes][dim].
+ * vfem_hom_apply: W_out[s] = K_per W_in[s], K_per the periodic stiffness matrix with the pin's row and column replaced by the identity.
+ * vfem_hom_solve_cells: K_per w_q = - sum_e E_e L[:, q] for all S cases together by block-Jacobi PCG from w = 0; a case is frozen
+ *   once |r| / |b| <= tol, the host tests convergence once every 8 iterations; error (with the worst case's residual in the message,
+ *   the two output arrays filled) when a case has not converged after max_iter iterations.  Results are bit-identical run to run.
+ * vfem_hom_tensor: Eh[q][r] = (1 / cell_volume) sum_e E_e (w_{q,e} . L[:, r] + vol D[q][r]) to the host (not symmetrised).
+ * vfem_hom_tensor_gradient: G (device) [prod(nelems)][S][S] = dE[e] / cell_volume *
+ *   (w_{q,e}^T K0 w_{r,e} + w_{q,e} . L[:, r] + L[:, q] . w_{r,e} + vol D[q][r]), upper triangle mirrored; dE (device, dE_e / drho_e)
+ *   may be NULL for a factor 1.  sum_e E_e G_e (dE = NULL) = Eh at the exact solution. */
+int vfem_hom_apply(int dim, const int64_t *nelems_host, const double *K0_host, const double *L_host, const double *D_host, double vol,
+                   const double *E, const double *W_in, double *W_out, void *stream);
+int vfem_hom_solve_cells(int dim, const int64_t *nelems_host, const double *K0_host, const double *L_host, const double *D_host,
+                         double vol, const double *E, double *W, double tol, int max_iter, int *iterations_out_host,
+                         double *relres_out_host, void *stream);
+int vfem_hom_tensor(int dim, const int64_t *nelems_host, const double *K0_host, const double *L_host, const double *D_host, double vol,
+                    const double *E, const double *W, double cell_volume, double *Eh_host, void *stream);
+int vfem_hom_tensor_gradient(int dim, const int64_t *nelems_host, const double *K0_host, const double *L_host, const double *D_host,
+                             double vol, const double *E, const double *W, double cell_volume, const double *dE, double *G,
+                             void *stream);
+
 /* ---- timers: BENCHMARK_* registry (MeshFEM GlobalBenchmark.hh / Timer.hh; VoxelFEM.cc:245-255) ---- */
 int vfem_timers_reset(void);
 int vfem_timers_report(char *buf_host, size_t buf_len);

@@ -26,6 +26,9 @@ class _DL(ctypes.Structure):
     _fields_ = [("n_planes", c_int64), ("plane_nodes", c_int64), ("first_owned", c_int64), ("last_owned", c_int64), ("xoffn", c_int64),
                 ("gl", ctypes.c_int32), ("gr", ctypes.c_int32), ("x", c_void_p), ("b", c_void_p), ("r", c_void_p)]
 
+# what every vfem_hom_* entry point starts with: dim, nelems, K0, L, D (host), vol, moduli (device)
+_HOM = [c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double), POINTER(c_double), c_double, c_void_p]
+
 # name -> (restype, argtypes); kept in one table so tests can check it against include/vfem.h
 SIGNATURES = {
     "vfem_last_error": (c_char_p, []),
@@ -175,6 +178,10 @@ SIGNATURES = {
     "vfem_mlp_forward_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "vfem_mlp_forward_grid": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_double), POINTER(c_double), c_void_p,
                                       c_void_p, c_void_p]),
+    "vfem_hom_apply": (c_int, _HOM + [c_void_p, c_void_p, c_void_p]),
+    "vfem_hom_solve_cells": (c_int, _HOM + [c_void_p, c_double, c_int, POINTER(c_int), POINTER(c_double), c_void_p]),
+    "vfem_hom_tensor": (c_int, _HOM + [c_void_p, c_double, POINTER(c_double), c_void_p]),
+    "vfem_hom_tensor_gradient": (c_int, _HOM + [c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
     "vfem_timers_reset": (c_int, []),
     "vfem_timers_report": (c_int, [c_char_p, c_size_t]),
 }

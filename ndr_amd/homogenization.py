@@ -1,0 +1,174 @@
+"""Periodic homogenisation of a voxel cell (``VoxelFEM/TPPeriodicHomogenization.hh`` and ``TensorProjection.hh`` of the reference).
+
+    w  = solveCellProblems(sim)                       # S fluctuation fields, S = 3 (2-D) or 6 (3-D)
+    Eh = homogenizedElasticityTensor(w, sim)          # an ElasticityTensor: the base material of a macro-scale run
+    dE = homogenizedElasticityTensorGradient(w, sim)  # [numElements, S, S]: d Eh / d rho_e
+
+for a degree-1 simulator in 2-D or 3-D holding any material.  The numerics run in ``libvfem.so`` (``vfem_hom_*``, include/vfem.h)
+on the PERIODIC node grid: node (i_0, ..) of the simulator's grid is the unknown (i_d mod ne_d), node 0 is pinned.  The simulator
+is only read: its Dirichlet conditions and loads play no part and stay as they are.
+
+The element modulus  E_e = E_min + rho_e^gamma (E_0 - E_min)  scales the stiffness, the load and the tensor alike.  (The
+reference scales load and tensor by the raw density and the stiffness by the SIMP modulus, which agrees with this only for
+gamma = 1, E_0 = 1, E_min = 0.)  Strain cases follow ``ndr_amd.materials``: xx yy xy / xx yy zz yz xz xy; the unit strain of a
+shear case has 0.5 on both off-diagonal entries.  DESIGN "Periodic homogenisation" has the formulas.
+
+Fields cross this boundary on the simulator's FULL node grid with the duplicate faces filled, like every other nodal field of the
+package: numpy arrays ``[numNodes, N]`` per strain case, or one torch tensor ``[S, numNodes, N]`` for the ``*_device`` variants.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+from . import materials as _materials
+from .pyVoxelFEM import _dev, _ptr, _stream, _stress_load, _to_np
+
+__all__ = ["solveCellProblems", "solveCellProblems_device", "homogenizedElasticityTensor", "homogenizedElasticityTensor_device",
+           "homogenizedElasticityTensorGradient", "homogenizedElasticityTensorGradient_device", "closestIsotropicTensor",
+           "last_iterations", "last_relative_residuals"]
+
+last_iterations = []             # PCG iterations of each strain case in the last solveCellProblems
+last_relative_residuals = []     # |r| / |b| of each strain case at its end
+
+
+def _dp(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+class _Cell:
+    """what every ``vfem_hom_*`` call starts with, taken from a simulator: the grid, K0, L, D, the voxel volume, the moduli"""
+
+    def __init__(self, sim):
+        N = getattr(sim, "N", None)
+        if N not in (2, 3) or getattr(sim, "P", None) != 1:
+            raise RuntimeError("periodic homogenisation needs a degree-1 simulator (TensorProductSimulator1_1 or 1_1_1)")
+        if sim._num_stored_elements() != sim.numElements():
+            raise RuntimeError("periodic homogenisation needs a whole cell: this simulator stores slab padding layers")
+        ne = [int(n) for n in sim.NbElementsPerDimension()]
+        if min(ne) < 2:
+            raise RuntimeError("periodic homogenisation needs at least 2 elements along every axis (got %s)" % "x".join(map(str, ne)))
+        self.N, self.S, self.ne = N, 3 if N == 2 else 6, ne
+        self.pn = int(np.prod(ne))
+        h = (sim._bbmax - sim._bbmin) / np.asarray(ne, dtype=np.float64)
+        self.vol = float(np.prod(h))
+        self.cell_volume = self.vol * self.pn
+        tensor = sim.ETensor
+        self.D = np.ascontiguousarray(tensor.D)
+        self.K0 = np.ascontiguousarray(sim.fullDensityElementStiffnessMatrix())
+        # L[:, q]: element load of the constant stress C : e_q, e_q = SymmetricMatrix::CanonicalBasis(q)
+        one = torch.ones((1,) * N, dtype=torch.float64)
+        L = np.empty((self.K0.shape[0], self.S))
+        for q, (i, j) in enumerate(_materials._PAIRS[N]):
+            eps = np.zeros((N, N))
+            eps[i, j] = eps[j, i] = 1.0 if i == j else 0.5
+            L[:, q] = _stress_load(tensor.doubleContract(eps), h, 1, one).numpy().reshape(-1)
+        self.L = np.ascontiguousarray(L)
+        rho = sim.getDensities_device()[:self.pn]
+        E0, Emin, gamma = float(sim.E_0), float(sim.E_min), float(sim.gamma)
+        self.E = (Emin + rho ** gamma * (E0 - Emin)).contiguous()
+        self.dE = (gamma * rho ** (gamma - 1.0) * (E0 - Emin)).contiguous()
+        self._nelems = np.asarray(ne, dtype=np.int64)
+
+    def head(self):
+        return (self.N, self._nelems.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _dp(self.K0), _dp(self.L), _dp(self.D), self.vol,
+                _ptr(self.E))
+
+    # ---- full node grid <-> periodic node grid ----
+    def to_full(self, Wp):
+        """[S, periodic nodes, N] -> [S, numNodes, N]: the duplicate faces filled"""
+        W = Wp.reshape([Wp.shape[0]] + self.ne + [self.N])
+        for d, n in enumerate(self.ne):
+            W = W.index_select(d + 1, torch.arange(n + 1, device=W.device) % n)
+        return W.reshape(Wp.shape[0], -1, self.N).contiguous()
+
+    def to_periodic(self, W):
+        """[S, numNodes, N] -> [S, periodic nodes, N]: the first copy of every periodic node"""
+        if not isinstance(W, torch.Tensor):
+            W = torch.from_numpy(np.ascontiguousarray(np.asarray(W, dtype=np.float64)))
+        W = W.to(device=_dev(), dtype=torch.float64)
+        nn = int(np.prod([n + 1 for n in self.ne]))
+        if W.numel() != self.S * nn * self.N:
+            raise RuntimeError("Invalid input size: expected %d fields of %d x %d values" % (self.S, nn, self.N))
+        W = W.reshape([self.S] + [n + 1 for n in self.ne] + [self.N])
+        for d, n in enumerate(self.ne):
+            W = W.narrow(d + 1, 0, n)
+        return W.reshape(self.S, self.pn, self.N).contiguous()
+
+
+def solveCellProblems_device(sim, tol=1e-10, maxIter=20000):
+    """the S fluctuation fields as one device tensor [S, numNodes, N]; see ``solveCellProblems``"""
+    global last_iterations, last_relative_residuals
+    c = _Cell(sim)
+    Wp = torch.empty((c.S, c.pn, c.N), dtype=torch.float64, device=_dev())
+    its, res = (ctypes.c_int * c.S)(), (ctypes.c_double * c.S)()
+    status = _lib.load().vfem_hom_solve_cells(*c.head(), _ptr(Wp), float(tol), int(maxIter), its, res, _stream())
+    last_iterations, last_relative_residuals = list(its), list(res)
+    _lib.check(status)
+    return c.to_full(Wp)
+
+
+def solveCellProblems(sim, tol=1e-10, maxIter=20000):
+    """TPPeriodicHomogenization::solveCellProblems: for every unit strain e_q the periodic fluctuation w_q with
+    K_per w_q = - sum_e E_e L[:, q], w_q = 0 at node 0, by a batched block-Jacobi PCG to ``|r| / |b| <= tol``.  Returns a list of S
+    arrays [numNodes, N]; raises RuntimeError when a case has not converged after ``maxIter`` iterations.  The iteration counts and
+    final residuals are left in ``last_iterations`` / ``last_relative_residuals``.  ``sim`` is not changed."""
+    return list(_to_np(solveCellProblems_device(sim, tol, maxIter)))
+
+
+def _tensor_from(D, dim):
+    t = _materials.ElasticityTensor(dim=dim)
+    t._D, t._iso = np.array(D, dtype=np.float64), None           # as computed: ``fromD`` would refuse the unsymmetrised matrix
+    return t
+
+
+def homogenizedElasticityTensor_device(w, sim, baseCellVolume=0.0):
+    c = _Cell(sim)
+    Wp = c.to_periodic(w)
+    Eh = np.empty((c.S, c.S))
+    _lib.check(_lib.load().vfem_hom_tensor(*c.head(), _ptr(Wp), float(baseCellVolume) or c.cell_volume, _dp(Eh), _stream()))
+    return _tensor_from(Eh, c.N)
+
+
+def homogenizedElasticityTensor(w, sim, baseCellVolume=0.0):
+    """TPPeriodicHomogenization::homogenizedElasticityTensor (stress-like):
+    Eh[q, r] = 1/|Y| sum_e E_e (w_{q,e} . L[:, r] + vol D[q, r]), |Y| = ``baseCellVolume`` or the bounding box's volume.
+    The result is as computed, not symmetrised (its asymmetry is the solver's residual)."""
+    return homogenizedElasticityTensor_device(np.stack([np.asarray(a, dtype=np.float64) for a in w]), sim, baseCellVolume)
+
+
+def _gradient(w, sim, scaled):
+    c = _Cell(sim)
+    Wp = c.to_periodic(w)
+    G = torch.empty((c.pn, c.S, c.S), dtype=torch.float64, device=_dev())
+    _lib.check(_lib.load().vfem_hom_tensor_gradient(*c.head(), _ptr(Wp), c.cell_volume, _ptr(c.dE) if scaled else None, _ptr(G),
+                                                    _stream()))
+    return G
+
+
+def homogenizedElasticityTensorGradient_device(w, sim):
+    return _gradient(w, sim, True)
+
+
+def homogenizedElasticityTensorGradient(w, sim):
+    """TPPeriodicHomogenization::homogenizedElasticityTensorGradient: [numElements, S, S], the derivative of the homogenised tensor
+    with respect to every density, dE_e/drho_e / |Y| (w_q^T K0 w_r + w_q . L[:, r] + L[:, q] . w_r + vol D[q, r]) on element e"""
+    return _to_np(_gradient(np.stack([np.asarray(a, dtype=np.float64) for a in w]), sim, True))
+
+
+def closestIsotropicTensor(C):
+    """TensorProjection.hh:22-76: the isotropic tensor closest to ``C`` in the Frobenius norm of the rank-4 tensors.  With the
+    hydrostatic and deviatoric extractors J, K (orthogonal, <J, J> = 1, <K, K> = n (n + 1) / 2 - 1):
+    n lambda + 2 mu = <C, J> = C_iijj / n and 2 mu = <C, K> / <K, K> = (C_ijij - C_iijj / n) / <K, K>."""
+    if not isinstance(C, _materials.ElasticityTensor):
+        raise TypeError("closestIsotropicTensor takes an ndr_amd.ElasticityTensor")
+    n = C.dim
+    full = C.fullTensor()
+    c_ijij, c_iijj = float(np.einsum("ijij->", full)), float(np.einsum("iijj->", full))
+    alpha = c_iijj / n
+    beta = (c_ijij - alpha) / (0.5 * (n * n + n) - 1.0)
+    out = _materials.ElasticityTensor(dim=n)
+    out._set_lame((alpha - beta) / n, beta / 2.0)
+    out._iso = None
+    return out
