@@ -36,6 +36,7 @@ typedef struct vfem_mg  vfem_mg;      /* MultigridSolver<1,1,1>                 
 typedef struct vfem_mlp vfem_mlp;     /* networks.MLP (Fourier features + ReLU MLP)                (networks.py:128) */
 typedef struct vfem_gsim vfem_gsim;   /* TensorProductSimulator<p,..,p>, N = 2 or 3, p = 1 or 2; <2,2,2> = 27-node hexahedra,
                                          unbound in the reference (VoxelFEM.cc:226-229) */
+typedef struct vfem_hom_mg vfem_hom_mg; /* the multigrid hierarchy of one periodic cell (vfem_hom_mg_*) */
 typedef struct vfem_gmg vfem_gmg;     /* MultigridSolver<p,..,p> of the generic path */
 
 const char *vfem_last_error(void);
@@ -484,6 +485,38 @@ int vfem_hom_tensor(int dim, const int64_t *nelems_host, const double *K0_host, 
 int vfem_hom_tensor_gradient(int dim, const int64_t *nelems_host, const double *K0_host, const double *L_host, const double *D_host,
                              double vol, const double *E, const double *W, double cell_volume, const double *dE, double *G,
                              void *stream);
+
+/* ---- multigrid-preconditioned PCG for the cell problems (DESIGN "Periodic homogenisation") ----
+ * vfem_hom_mg_create builds the hierarchy of one cell from the arguments every vfem_hom_* call starts with; the handle keeps the
+ * pointer E (device), which must stay valid and unchanged until vfem_hom_mg_destroy.  Level 0 is the cell (matrix-free); level
+ * l + 1 has n_d / 2 periodic nodes per axis and stores the Galerkin operator P^T A_l P, P the periodic N-linear interpolation.  A
+ * level is coarsened while every n_d is even and at least 4 and fewer than max_coarsenings coarsenings are made (negative: no
+ * cap).  The last level is solved exactly by a dense inverse: error when it has more dofs than that solver takes (the message names
+ * the level sizes and the limit).  On every level node 0 is pinned: the operator's row and column of node 0 are the identity.
+ * Vectors of level l (device) are [S][nodes_l][dim].
+ * vfem_hom_mg_level_dims: n_out[dim] = nodes per axis of level l.  vfem_hom_mg_bytes: device memory the handle holds.
+ * vfem_hom_mg_level_apply: W_out = A_l W_in.
+ * vfem_hom_mg_smooth: one 2^dim-colour block Gauss-Seidel sweep of A_l X = B on X (colour = parity of the node index per axis, axis 0
+ *   the most significant bit), colours ascending (forward != 0) or descending; every n_d of the level must be even.
+ * vfem_hom_mg_restrict: coarse (level l + 1) = P^T fine (level l), zero at node 0.  vfem_hom_mg_prolong_add: fine += P coarse, the
+ *   coarse value of node 0 counting as zero.
+ * vfem_hom_mg_vcycle: X = V-cycle(B) on level 0 from a zero initial guess: `smoothing` ascending sweeps, the coarse correction,
+ *   `smoothing` descending sweeps; a symmetric positive definite operator.  A one-level hierarchy applies the exact inverse.
+ * vfem_hom_mg_solve_cells: vfem_hom_solve_cells with z = V-cycle(r) as the preconditioner; same freeze criterion, outputs and errors.
+ * Results are bit-identical run to run. */
+int vfem_hom_mg_create(vfem_hom_mg **out, int dim, const int64_t *nelems_host, const double *K0_host, const double *L_host,
+                       const double *D_host, double vol, const double *E, int max_coarsenings, void *stream);
+int vfem_hom_mg_destroy(vfem_hom_mg *h);
+int vfem_hom_mg_num_levels(vfem_hom_mg *h);
+int64_t vfem_hom_mg_bytes(vfem_hom_mg *h);
+int vfem_hom_mg_level_dims(vfem_hom_mg *h, int l, int64_t *n_out);
+int vfem_hom_mg_level_apply(vfem_hom_mg *h, int l, const double *W_in, double *W_out, void *stream);
+int vfem_hom_mg_smooth(vfem_hom_mg *h, int l, double *X, const double *B, int forward, void *stream);
+int vfem_hom_mg_restrict(vfem_hom_mg *h, int l, const double *fine, double *coarse, void *stream);
+int vfem_hom_mg_prolong_add(vfem_hom_mg *h, int l, const double *coarse, double *fine, void *stream);
+int vfem_hom_mg_vcycle(vfem_hom_mg *h, const double *B, double *X, int smoothing, void *stream);
+int vfem_hom_mg_solve_cells(vfem_hom_mg *h, double *W, double tol, int max_iter, int smoothing, int *iterations_out_host,
+                            double *relres_out_host, void *stream);
 
 /* ---- timers: BENCHMARK_* registry (MeshFEM GlobalBenchmark.hh / Timer.hh; VoxelFEM.cc:245-255) ---- */
 int vfem_timers_reset(void);

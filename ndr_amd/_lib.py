@@ -182,6 +182,17 @@ SIGNATURES = {
     "vfem_hom_solve_cells": (c_int, _HOM + [c_void_p, c_double, c_int, POINTER(c_int), POINTER(c_double), c_void_p]),
     "vfem_hom_tensor": (c_int, _HOM + [c_void_p, c_double, POINTER(c_double), c_void_p]),
     "vfem_hom_tensor_gradient": (c_int, _HOM + [c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
+    "vfem_hom_mg_create": (c_int, [POINTER(c_void_p)] + _HOM + [c_int, c_void_p]),
+    "vfem_hom_mg_destroy": (c_int, [c_void_p]),
+    "vfem_hom_mg_num_levels": (c_int, [c_void_p]),
+    "vfem_hom_mg_bytes": (c_int64, [c_void_p]),
+    "vfem_hom_mg_level_dims": (c_int, [c_void_p, c_int, POINTER(c_int64)]),
+    "vfem_hom_mg_level_apply": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "vfem_hom_mg_smooth": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "vfem_hom_mg_restrict": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "vfem_hom_mg_prolong_add": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "vfem_hom_mg_vcycle": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "vfem_hom_mg_solve_cells": (c_int, [c_void_p, c_void_p, c_double, c_int, c_int, POINTER(c_int), POINTER(c_double), c_void_p]),
     "vfem_timers_reset": (c_int, []),
     "vfem_timers_report": (c_int, [c_char_p, c_size_t]),
 }

@@ -47,6 +47,14 @@ inline void hom_build_stencil(int N, const double *K0, double *stencil) {
         }
 }
 
+// the checked arguments every vfem_hom_* entry point starts with, the element tables on the device (hom.hip)
+struct HomCall {
+    HomProblem p;
+    DevBuf<double> tables;          // K0 | L | D | stencil
+};
+void hom_setup(HomCall &c, const char *who, int dim, const int64_t *nelems, const double *K0, const double *L, const double *D,
+               double vol, const double *E, hipStream_t s);
+
 constexpr int HOM_THREADS = 256;
 inline int hom_node_blocks(const HomProblem &p) { return (p.pn + HOM_THREADS - 1) / HOM_THREADS; }
 // the tensor reduction walks the elements with a grid of fixed size (a function of the cell alone: the summation order is fixed)

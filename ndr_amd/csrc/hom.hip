@@ -7,13 +7,7 @@
 
 using namespace vfem;
 
-namespace {
-
-// the checked arguments of one call with its element tables on the device
-struct HomCall {
-    HomProblem p;
-    DevBuf<double> tables;          // K0 | L | D | stencil
-};
+namespace vfem {
 
 void hom_setup(HomCall &c, const char *who, int dim, const int64_t *nelems, const double *K0, const double *L, const double *D,
                double vol, const double *E, hipStream_t s) {
@@ -54,6 +48,10 @@ void hom_setup(HomCall &c, const char *who, int dim, const int64_t *nelems, cons
     p.D = c.tables.p + nk + nl;
     p.stencil = c.tables.p + nk + nl + nd;
 }
+
+}  // namespace vfem
+
+namespace {
 
 double cell_volume_of(const HomProblem &p, double cell_volume, const char *who) {
     if (!(cell_volume > 0.0) || !std::isfinite(cell_volume)) throw Error(std::string(who) + ": the cell volume must be positive");

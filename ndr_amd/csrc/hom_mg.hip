@@ -1,0 +1,286 @@
+// The multigrid-preconditioned PCG of the periodic cell problems (include/vfem.h: vfem_hom_mg_*; DESIGN "Periodic homogenisation").
+// A handle holds the hierarchy of one cell: level 0 matrix-free, Galerkin levels stored (hom_mg.h), the coarsest level as a dense
+// inverse (CoarsestSolver).  It is built once per solve; the moduli it reads at level 0 stay the caller's.
+#include "hom_mg.h"
+#include "vfem_host.h"
+
+#include <cmath>
+#include <memory>
+
+using namespace vfem;
+
+struct HomMgLevel {
+    HomGrid g;
+    DevBuf<double> A;               // levels >= 1: [3^N][N][N][nodes], the unpinned Galerkin operator
+    DevBuf<double> Dinv;            // levels >= 1: [N N][nodes]
+    DevBuf<double> x, b, r;         // levels >= 1: [S][nodes][N] (r: smoothed levels only)
+};
+
+struct vfem_hom_mg {
+    HomCall call;                   // level 0: the cell, its tables, the caller's moduli
+    std::vector<HomMgLevel> lv;
+    DevBuf<double> Minv0, r0;       // level 0: launch_hom_jacobi's inverses and the residual (hierarchies of more than one level)
+    DevBuf<uint8_t> pin;            // coarsest level: the mask with node 0 fixed
+    CoarsestSolver coarsest;
+    int N() const { return call.p.N; }
+    int L() const { return (int) lv.size() - 1; }
+    HomBlocks blocks(int l) const { return l == 0 ? HomBlocks{call.p.stencil, call.p.E} : HomBlocks{lv[l].A.p, nullptr}; }
+    HomDinv dinv(int l) const {
+        const long long nn = (long long) N() * N();
+        return l == 0 ? HomDinv{Minv0.p, nn, 1} : HomDinv{lv[l].Dinv.p, 1, lv[l].g.pn};
+    }
+    size_t vec(int l) const { return (size_t) lv[l].g.S * lv[l].g.pn * lv[l].g.N; }
+    long long bytes() const {
+        size_t n = call.tables.n + Minv0.n + r0.n;
+        for (const HomMgLevel &v : lv) n += v.A.n + v.Dinv.n + v.x.n + v.b.n + v.r.n;
+        return (long long) (n * sizeof(double)) + coarsest.bytes() + (long long) pin.n;
+    }
+};
+
+namespace {
+
+std::string dims_text(const HomGrid &g) {
+    std::string t = std::to_string(g.n[0]);
+    for (int d = 1; d < g.N; ++d) t += "x" + std::to_string(g.n[d]);
+    return t;
+}
+
+bool can_colour(const HomGrid &g) {
+    for (int d = 0; d < g.N; ++d)
+        if (g.n[d] % 2) return false;
+    return true;
+}
+
+void check_level(const vfem_hom_mg *h, int l, const char *who, int last) {
+    if (!h) throw Error(std::string(who) + ": null handle");
+    if (l < 0 || l > last) throw Error(std::string(who) + ": level " + std::to_string(l) + " out of range");
+}
+
+// one sweep over the 2^N colours, ascending (forward) or descending
+void sweep(vfem_hom_mg *h, int l, double *x, const double *b, int forward, hipStream_t s) {
+    const int nc = 1 << h->N();
+    for (int k = 0; k < nc; ++k)
+        launch_hom_mg_sweep_colour(h->lv[l].g, h->blocks(l), h->dinv(l), forward ? k : nc - 1 - k, x, b, s);
+}
+
+void coarse_solve(vfem_hom_mg *h, const double *b, double *x, hipStream_t s) {
+    if (h->coarsest.held != CoarsestSolver::DENSE) throw Error("the coarsest level holds no dense inverse");
+    launch_hom_mg_gemv(h->lv.back().g, h->coarsest.Ainv.p, b, x, s);
+}
+
+// X = V-cycle(B) from a zero initial guess: `smoothing` ascending sweeps, the coarse correction, `smoothing` descending sweeps
+void vcycle(vfem_hom_mg *h, const double *B, double *X, int smoothing, hipStream_t s) {
+    const int L = h->L();
+    if (L == 0) { coarse_solve(h, B, X, s); return; }
+    for (int l = 0; l < L; ++l) {
+        double *x = l == 0 ? X : h->lv[l].x.p;
+        const double *b = l == 0 ? B : h->lv[l].b.p;
+        double *r = l == 0 ? h->r0.p : h->lv[l].r.p;
+        VFEM_HIP(hipMemsetAsync(x, 0, h->vec(l) * sizeof(double), s));
+        for (int k = 0; k < smoothing; ++k) sweep(h, l, x, b, 1, s);
+        launch_hom_mg_residual(h->lv[l].g, h->blocks(l), x, b, r, s);
+        launch_hom_mg_restrict(h->lv[l].g, h->lv[l + 1].g, r, h->lv[l + 1].b.p, s);
+    }
+    coarse_solve(h, h->lv[L].b.p, h->lv[L].x.p, s);
+    for (int l = L - 1; l >= 0; --l) {
+        double *x = l == 0 ? X : h->lv[l].x.p;
+        const double *b = l == 0 ? B : h->lv[l].b.p;
+        launch_hom_mg_prolong_add(h->lv[l].g, h->lv[l + 1].g, h->lv[l + 1].x.p, x, s);
+        for (int k = 0; k < smoothing; ++k) sweep(h, l, x, b, 0, s);
+    }
+}
+
+void check_smoothing(int smoothing, const char *who) {
+    if (smoothing < 1 || smoothing > 16) throw Error(std::string(who) + ": smoothing must be in [1, 16]");
+}
+
+}  // namespace
+
+extern "C" {
+
+int vfem_hom_mg_create(vfem_hom_mg **out, int dim, const int64_t *nelems_host, const double *K0_host, const double *L_host,
+                       const double *D_host, double vol, const double *E, int max_coarsenings, void *stream) {
+    VFEM_TRY
+    if (!out) throw Error("vfem_hom_mg_create: null argument");
+    *out = nullptr;
+    hipStream_t s = S(stream);
+    std::unique_ptr<vfem_hom_mg> h(new vfem_hom_mg);
+    hom_setup(h->call, "vfem_hom_mg_create", dim, nelems_host, K0_host, L_host, D_host, vol, E, s);
+    const HomProblem &p = h->call.p;
+    const int N = p.N;
+    // the levels: coarsened while every n_d is even and at least 4 (max_coarsenings < 0: as far as that allows)
+    HomGrid g{N, p.S, {p.n[0], p.n[1], N == 3 ? p.n[2] : 1}, p.pn};
+    std::string sizes = dims_text(g);
+    h->lv.emplace_back();
+    h->lv.back().g = g;
+    while (max_coarsenings < 0 || (int) h->lv.size() - 1 < max_coarsenings) {
+        bool ok = true;
+        for (int d = 0; d < N; ++d) ok = ok && g.n[d] % 2 == 0 && g.n[d] >= 4;
+        if (!ok) break;
+        g.pn = 1;
+        for (int d = 0; d < N; ++d) { g.n[d] /= 2; g.pn *= g.n[d]; }
+        h->lv.emplace_back();
+        h->lv.back().g = g;
+        sizes += ", " + dims_text(g);
+    }
+    const int L = h->L();
+    const long long nc = (long long) g.pn * N;
+    if (nc > DENSE_COARSEST_MAX_DOFS)
+        throw Error("vfem_hom_mg_create: the coarsest level of the hierarchy " + sizes + " has " + std::to_string(nc) +
+                    " dofs, above the limit of " + std::to_string(DENSE_COARSEST_MAX_DOFS) +
+                    " of the dense coarsest-level solve (a level is coarsened only while every extent is even and at least 4)");
+    const int noff = N == 2 ? 9 : 27;
+    if (L > 0) {
+        h->Minv0.alloc((size_t) p.pn * N * N);
+        h->r0.alloc(h->vec(0));
+        launch_hom_jacobi(p, h->Minv0.p, s);
+    }
+    for (int l = 1; l <= L; ++l) {
+        HomMgLevel &v = h->lv[l];
+        v.A.alloc((size_t) noff * N * N * v.g.pn);
+        v.Dinv.alloc((size_t) N * N * v.g.pn);
+        v.x.alloc(h->vec(l));
+        v.b.alloc(h->vec(l));
+        if (l < L) v.r.alloc(h->vec(l));
+        launch_hom_mg_galerkin(h->lv[l - 1].g, v.g, h->blocks(l - 1), v.A.p, s);
+        launch_hom_mg_dinv(v.g, v.A.p, v.Dinv.p, s);
+    }
+    // the coarsest level: the dense pinned matrix, inverted; the rows and columns of the pin zeroed in the inverse
+    std::vector<uint8_t> mask((size_t) g.pn, 0);
+    mask[0] = (uint8_t) ((1 << N) - 1);
+    h->pin.alloc(mask.size());
+    VFEM_HIP(hipMemcpyAsync(h->pin.p, mask.data(), mask.size(), hipMemcpyHostToDevice, s));
+    double *M = h->coarsest.dense_matrix(nc, s);
+    launch_hom_mg_dense(g, h->blocks(L), M, s);
+    h->coarsest.factor_dense(N, h->pin.p, s);
+    VFEM_HIP(hipStreamSynchronize(s));          // `mask` goes out of scope; the factorisation's workspace is not needed again
+    h->coarsest.work = DenseWork();
+    *out = h.release();
+    VFEM_CATCH
+}
+
+int vfem_hom_mg_destroy(vfem_hom_mg *h) {
+    VFEM_TRY
+    delete h;
+    VFEM_CATCH
+}
+
+int vfem_hom_mg_num_levels(vfem_hom_mg *h) { return h ? (int) h->lv.size() : 0; }
+
+int64_t vfem_hom_mg_bytes(vfem_hom_mg *h) { return h ? h->bytes() : 0; }
+
+int vfem_hom_mg_level_dims(vfem_hom_mg *h, int l, int64_t *n_out) {
+    VFEM_TRY
+    check_level(h, l, "vfem_hom_mg_level_dims", h ? h->L() : 0);
+    if (!n_out) throw Error("vfem_hom_mg_level_dims: null argument");
+    for (int d = 0; d < h->N(); ++d) n_out[d] = h->lv[l].g.n[d];
+    VFEM_CATCH
+}
+
+int vfem_hom_mg_level_apply(vfem_hom_mg *h, int l, const double *W_in, double *W_out, void *stream) {
+    VFEM_TRY
+    check_level(h, l, "vfem_hom_mg_level_apply", h ? h->L() : 0);
+    if (!W_in || !W_out || W_in == W_out) throw Error("vfem_hom_mg_level_apply: W_in and W_out must be two arrays");
+    if (l == 0) launch_hom_apply(h->call.p, W_in, W_out, nullptr, S(stream));
+    else launch_hom_mg_apply(h->lv[l].g, h->lv[l].A.p, W_in, W_out, S(stream));
+    VFEM_CATCH
+}
+
+int vfem_hom_mg_smooth(vfem_hom_mg *h, int l, double *X, const double *B, int forward, void *stream) {
+    VFEM_TRY
+    check_level(h, l, "vfem_hom_mg_smooth", h ? h->L() : 0);
+    if (!X || !B) throw Error("vfem_hom_mg_smooth: null argument");
+    if (!can_colour(h->lv[l].g)) throw Error("vfem_hom_mg_smooth: the colour sweep needs an even extent along every axis (level " + dims_text(h->lv[l].g) + ")");
+    if (l == 0 && !h->Minv0.p) {                // a one-level hierarchy never smooths: the inverses are made on demand
+        h->Minv0.alloc((size_t) h->call.p.pn * h->N() * h->N());
+        launch_hom_jacobi(h->call.p, h->Minv0.p, S(stream));
+    }
+    sweep(h, l, X, B, forward, S(stream));
+    VFEM_CATCH
+}
+
+int vfem_hom_mg_restrict(vfem_hom_mg *h, int l, const double *fine, double *coarse, void *stream) {
+    VFEM_TRY
+    check_level(h, l, "vfem_hom_mg_restrict", h ? h->L() - 1 : 0);
+    if (!fine || !coarse) throw Error("vfem_hom_mg_restrict: null argument");
+    launch_hom_mg_restrict(h->lv[l].g, h->lv[l + 1].g, fine, coarse, S(stream));
+    VFEM_CATCH
+}
+
+int vfem_hom_mg_prolong_add(vfem_hom_mg *h, int l, const double *coarse, double *fine, void *stream) {
+    VFEM_TRY
+    check_level(h, l, "vfem_hom_mg_prolong_add", h ? h->L() - 1 : 0);
+    if (!fine || !coarse) throw Error("vfem_hom_mg_prolong_add: null argument");
+    launch_hom_mg_prolong_add(h->lv[l].g, h->lv[l + 1].g, coarse, fine, S(stream));
+    VFEM_CATCH
+}
+
+int vfem_hom_mg_vcycle(vfem_hom_mg *h, const double *B, double *X, int smoothing, void *stream) {
+    VFEM_TRY
+    if (!h || !B || !X || B == X) throw Error("vfem_hom_mg_vcycle: B and X must be two arrays");
+    check_smoothing(smoothing, "vfem_hom_mg_vcycle");
+    vcycle(h, B, X, smoothing, S(stream));
+    VFEM_CATCH
+}
+
+int vfem_hom_mg_solve_cells(vfem_hom_mg *h, double *W, double tol, int max_iter, int smoothing, int *iterations_out_host,
+                            double *relres_out_host, void *stream) {
+    VFEM_TRY
+    hipStream_t s = S(stream);
+    if (!h || !W || !iterations_out_host || !relres_out_host) throw Error("vfem_hom_mg_solve_cells: null argument");
+    if (!(tol > 0.0) || max_iter < 1) throw Error("vfem_hom_mg_solve_cells: tol must be positive and max_iter at least 1");
+    check_smoothing(smoothing, "vfem_hom_mg_solve_cells");
+    const HomProblem &p = h->call.p;
+    const HomGrid &g = h->lv[0].g;
+    const size_t nv = h->vec(0);
+    const int nb = hom_node_blocks(p);
+    DevBuf<double> r, z, pv, Ap, partial;
+    DevBuf<HomState> st;
+    r.alloc(nv); z.alloc(nv); pv.alloc(nv); Ap.alloc(nv);
+    partial.alloc((size_t) 2 * p.S * nb);
+    st.alloc(1);
+    st.zero(s); pv.zero(s);
+    VFEM_HIP(hipMemsetAsync(W, 0, nv * sizeof(double), s));
+    // the loop of vfem_hom_solve_cells with z = V-cycle(r): x = 0, r = b, p = z
+    launch_hom_rhs(p, r.p, s);
+    vcycle(h, r.p, z.p, smoothing, s);
+    launch_hom_mg_dots(g, r.p, z.p, partial.p, s);
+    launch_hom_finish_beta(p, partial.p, st.p, tol, 1, s);
+    launch_hom_direction(p, z.p, pv.p, st.p, s);
+    HomState hs;
+    auto read_state = [&]() {
+        VFEM_HIP(hipMemcpyAsync(&hs, st.p, sizeof(HomState), hipMemcpyDeviceToHost, s));
+        VFEM_HIP(hipStreamSynchronize(s));
+        for (int q = 0; q < p.S; ++q)
+            if (hs.active[q]) return true;
+        return false;
+    };
+    bool running = read_state();
+    for (int it = 1; running && it <= max_iter; ++it) {
+        launch_hom_apply(p, pv.p, Ap.p, partial.p, s);
+        launch_hom_finish_alpha(p, partial.p, st.p, s);
+        launch_hom_mg_update(g, pv.p, Ap.p, W, r.p, st.p, s);
+        vcycle(h, r.p, z.p, smoothing, s);
+        launch_hom_mg_dots(g, r.p, z.p, partial.p, s);
+        launch_hom_finish_beta(p, partial.p, st.p, tol, 0, s);
+        launch_hom_direction(p, z.p, pv.p, st.p, s);
+        // the host looks at the residual norms once every 8 iterations (a frozen column no longer moves in between); a one-level
+        // hierarchy is the exact inverse and is done after the first
+        if (it % 8 == 0 || it == max_iter || (it == 1 && h->L() == 0)) running = read_state();
+    }
+    int worst = 0;
+    for (int q = 0; q < p.S; ++q) {
+        iterations_out_host[q] = hs.iters[q];
+        relres_out_host[q] = hs.bb[q] > 0.0 ? std::sqrt(hs.rr[q] / hs.bb[q]) : 0.0;
+        if (relres_out_host[q] > relres_out_host[worst]) worst = q;
+    }
+    if (running) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "vfem_hom_mg_solve_cells: no convergence in %d iterations: strain case %d has |r|/|b| = %.3e (tol %.3e)",
+                 max_iter, worst, relres_out_host[worst], tol);
+        throw Error(msg);
+    }
+    VFEM_CATCH
+}
+
+}  // extern "C"

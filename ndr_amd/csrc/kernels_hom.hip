@@ -1,6 +1,7 @@
 // Periodic homogenisation kernels (hom.h): the batched matrix-free periodic operator, its node-block Jacobi preconditioner, the
 // vector updates and two-stage reductions of the batched PCG, the homogenised tensor and its density gradient.
 //
+// (The device helpers shared with the multigrid kernels are in hom_device.h.)
 // Apply: one thread owns one periodic node and gathers.  It does not walk element by element: for each of the 3^N neighbour
 // offsets it first sums the N x N coefficient block  sum_e E_e K0[(own local node, .), (neighbour's local node, .)]  over the
 // incident elements, then multiplies the block with the neighbour's values of all S columns.  The moduli and the K0 entries
@@ -11,118 +12,11 @@
 //
 // Reductions: every block reduces its values in a fixed order (wave shuffles, then the waves in order) and writes one partial per
 // block; a second kernel sums the partials in a fixed order.  No floating-point atomics: results are bit-identical run to run.
-#include "hom.h"
-
-#include "device_utils.h"
+#include "hom_device.h"
 
 namespace vfem {
 
 namespace {
-
-constexpr int HOM_T = HOM_THREADS;
-
-template <int N>
-struct HomDims {
-    int n[N];
-    int pn;
-};
-
-template <int N>
-struct HomTraits {
-    static constexpr int S = N == 2 ? 3 : 6;
-    static constexpr int NPE = 1 << N;
-    static constexpr int KE = N * NPE;
-    static constexpr int NOFF = N == 2 ? 9 : 27;
-};
-
-// position (0 / 1) along axis d of local node a: axis 0 is the most significant bit (the last axis runs fastest)
-template <int N>
-__host__ __device__ constexpr int axis_bit(int a, int d) { return (a >> (N - 1 - d)) & 1; }
-
-template <int N>
-__device__ __forceinline__ int hom_flat(const HomDims<N> &g, const int c[N]) {
-    int f = c[0];
-#pragma unroll
-    for (int d = 1; d < N; ++d) f = f * g.n[d] + c[d];
-    return f;
-}
-
-// coordinates of periodic node / element t and, per axis, the wrapped coordinates at offsets -1, 0, +1
-template <int N>
-__device__ __forceinline__ void hom_neighbours(int t, const HomDims<N> &g, int nb[N][3]) {
-#pragma unroll
-    for (int d = N - 1; d >= 0; --d) {
-        const int c = t % g.n[d];
-        t /= g.n[d];
-        nb[d][0] = c == 0 ? g.n[d] - 1 : c - 1;
-        nb[d][1] = c;
-        nb[d][2] = c + 1 == g.n[d] ? 0 : c + 1;
-    }
-}
-
-// moduli of the 2^N elements incident to a node: in element a the node is local node a, i.e. the element sits one step
-// back along every axis whose bit is set
-template <int N>
-__device__ __forceinline__ void hom_incident_moduli(const HomDims<N> &g, const int nb[N][3], const double *__restrict__ E,
-                                                    double Ee[1 << N]) {
-#pragma unroll
-    for (int a = 0; a < (1 << N); ++a) {
-        int c[N];
-#pragma unroll
-        for (int d = 0; d < N; ++d) c[d] = nb[d][1 - axis_bit<N>(a, d)];
-        Ee[a] = E[hom_flat<N>(g, c)];
-    }
-}
-
-// flat indices of the 2^N nodes of element t (its first node has the element's own coordinates)
-template <int N>
-__device__ __forceinline__ void hom_element_nodes(const HomDims<N> &g, const int nb[N][3], int nd[1 << N]) {
-#pragma unroll
-    for (int m = 0; m < (1 << N); ++m) {
-        int c[N];
-#pragma unroll
-        for (int d = 0; d < N; ++d) c[d] = nb[d][1 + axis_bit<N>(m, d)];
-        nd[m] = hom_flat<N>(g, c);
-    }
-}
-
-// sum of M per-thread values over the block, in a fixed order; thread m < M writes value m to partial[m * stride + block]
-template <int M>
-__device__ __forceinline__ void block_reduce_store(double (&v)[M], double *__restrict__ partial, int stride) {
-    static_assert(M <= HOM_T, "one thread per value in the last step");
-    __shared__ double sh[M][HOM_T / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int m = 0; m < M; ++m) {
-        double x = v[m];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-        if (lane == 0) sh[m][wave] = x;
-    }
-    __syncthreads();
-    if ((int) threadIdx.x < M) {
-        double s = 0.0;
-#pragma unroll
-        for (int w = 0; w < HOM_T / 64; ++w) s += sh[threadIdx.x][w];
-        partial[(long long) threadIdx.x * stride + blockIdx.x] = s;
-    }
-}
-
-// sum of nb partials by one block of HOM_T threads, in a fixed order; every thread returns the sum
-__device__ __forceinline__ double sum_partials(const double *__restrict__ src, int nb) {
-    __shared__ double sh[HOM_T];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nb; i += HOM_T) s += src[i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = HOM_T / 2; w > 0; w >>= 1) {
-        if ((int) threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
 
 template <int N>
 __global__ __launch_bounds__(HOM_T) void k_hom_apply(HomDims<N> g, const double *__restrict__ stencil, const double *__restrict__ E,
@@ -162,15 +56,7 @@ __global__ __launch_bounds__(HOM_T) void k_hom_apply(HomDims<N> g, const double 
                 // the pin column: the neighbour's value counts as zero (a factor on the block: the loads stay unconditional)
                 const double unpinned = idx == 0 ? 0.0 : 1.0;
                 double B[N][N];
-#pragma unroll
-                for (int a = 0; a < N; ++a)
-#pragma unroll
-                    for (int b = 0; b < N; ++b) {
-                        double v = 0.0;
-#pragma unroll
-                        for (int ln = 0; ln < NPE; ++ln) v += Ee[ln] * tab[(ln * N + a) * N + b];
-                        B[a][b] = v * unpinned;
-                    }
+                hom_offset_block<N>(Ee, tab, unpinned, B);
 #pragma unroll
                 for (int s = 0; s < S; ++s) {
                     const double *ws = w + ((long long) s * g.pn + idx) * N;
@@ -221,22 +107,7 @@ __global__ __launch_bounds__(HOM_T) void k_hom_jacobi(HomDims<N> g, const double
             B[a][b] = v;
         }
     double I[N][N];
-    if constexpr (N == 2) {
-        const double r = 1.0 / (B[0][0] * B[1][1] - B[0][1] * B[1][0]);
-        I[0][0] = B[1][1] * r; I[0][1] = -B[0][1] * r;
-        I[1][0] = -B[1][0] * r; I[1][1] = B[0][0] * r;
-    } else {
-        const double c00 = B[1][1] * B[2][2] - B[1][2] * B[2][1], c01 = B[1][2] * B[2][0] - B[1][0] * B[2][2],
-                     c02 = B[1][0] * B[2][1] - B[1][1] * B[2][0];
-        const double r = 1.0 / (B[0][0] * c00 + B[0][1] * c01 + B[0][2] * c02);
-        I[0][0] = c00 * r; I[1][0] = c01 * r; I[2][0] = c02 * r;
-        I[0][1] = (B[0][2] * B[2][1] - B[0][1] * B[2][2]) * r;
-        I[1][1] = (B[0][0] * B[2][2] - B[0][2] * B[2][0]) * r;
-        I[2][1] = (B[0][1] * B[2][0] - B[0][0] * B[2][1]) * r;
-        I[0][2] = (B[0][1] * B[1][2] - B[0][2] * B[1][1]) * r;
-        I[1][2] = (B[0][2] * B[1][0] - B[0][0] * B[1][2]) * r;
-        I[2][2] = (B[0][0] * B[1][1] - B[0][1] * B[1][0]) * r;
-    }
+    hom_invert_block<N>(B, I);
 #pragma unroll
     for (int a = 0; a < N; ++a)
 #pragma unroll
@@ -431,14 +302,6 @@ __global__ __launch_bounds__(HOM_T) void k_hom_gradient(HomDims<N> g, const doub
             Ge[r * S + q] = v * scale;
         }
     }
-}
-
-template <int N>
-HomDims<N> dims_of(const HomProblem &p) {
-    HomDims<N> g;
-    for (int d = 0; d < N; ++d) g.n[d] = p.n[d];
-    g.pn = p.pn;
-    return g;
 }
 
 }  // namespace

@@ -27,10 +27,11 @@ from .pyVoxelFEM import _dev, _ptr, _stream, _stress_load, _to_np
 
 __all__ = ["solveCellProblems", "solveCellProblems_device", "homogenizedElasticityTensor", "homogenizedElasticityTensor_device",
            "homogenizedElasticityTensorGradient", "homogenizedElasticityTensorGradient_device", "closestIsotropicTensor",
-           "last_iterations", "last_relative_residuals"]
+           "last_iterations", "last_relative_residuals", "last_levels"]
 
 last_iterations = []             # PCG iterations of each strain case in the last solveCellProblems
 last_relative_residuals = []     # |r| / |b| of each strain case at its end
+last_levels = []                 # per-level cell sizes of the last multigrid solve: [[n_0, ..], [n_0 / 2, ..], ..]
 
 
 def _dp(a):
@@ -97,24 +98,101 @@ class _Cell:
         return W.reshape(self.S, self.pn, self.N).contiguous()
 
 
-def solveCellProblems_device(sim, tol=1e-10, maxIter=20000):
+class _Hierarchy:
+    """the multigrid hierarchy of one cell (``vfem_hom_mg_*``): level 0 is the cell, level l + 1 has half the periodic nodes per axis
+    and is made while every extent is even and at least 4 (``levels``: at most that many coarsenings), the last level is solved
+    exactly.  Vectors of level l are device tensors [S, nodes_l, N] on the periodic grid."""
+
+    def __init__(self, cell, levels=None):
+        self.cell = cell                                         # (keeps the moduli the handle reads alive)
+        self._lib = _lib.load()
+        self._h = ctypes.c_void_p()
+        cap = -1 if levels is None else int(levels)
+        if levels is not None and cap < 0:
+            raise ValueError("levels must be None or a non-negative number of coarsenings")
+        _lib.check(self._lib.vfem_hom_mg_create(ctypes.byref(self._h), *cell.head(), cap, _stream()))
+        n = (ctypes.c_int64 * cell.N)()
+        self.dims = []
+        for l in range(self._lib.vfem_hom_mg_num_levels(self._h)):
+            _lib.check(self._lib.vfem_hom_mg_level_dims(self._h, l, n))
+            self.dims.append(list(n))
+        self.bytes = int(self._lib.vfem_hom_mg_bytes(self._h))
+
+    def close(self):
+        if self._h:
+            self._lib.vfem_hom_mg_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        self.close()
+
+    def _like(self, l):
+        return torch.empty((self.cell.S, int(np.prod(self.dims[l])), self.cell.N), dtype=torch.float64, device=_dev())
+
+    def level_apply(self, l, W):
+        out = self._like(l)
+        _lib.check(self._lib.vfem_hom_mg_level_apply(self._h, l, _ptr(W), _ptr(out), _stream()))
+        return out
+
+    def smooth(self, l, X, B, forward=True):
+        """one colour sweep on X in place"""
+        _lib.check(self._lib.vfem_hom_mg_smooth(self._h, l, _ptr(X), _ptr(B), int(bool(forward)), _stream()))
+        return X
+
+    def restrict(self, l, fine):
+        out = self._like(l + 1)
+        _lib.check(self._lib.vfem_hom_mg_restrict(self._h, l, _ptr(fine), _ptr(out), _stream()))
+        return out
+
+    def prolong_add(self, l, coarse, fine):
+        _lib.check(self._lib.vfem_hom_mg_prolong_add(self._h, l, _ptr(coarse), _ptr(fine), _stream()))
+        return fine
+
+    def vcycle(self, B, smoothing=1):
+        out = self._like(0)
+        _lib.check(self._lib.vfem_hom_mg_vcycle(self._h, _ptr(B), _ptr(out), int(smoothing), _stream()))
+        return out
+
+    def solve(self, Wp, tol, maxIter, smoothing):
+        its, res = (ctypes.c_int * self.cell.S)(), (ctypes.c_double * self.cell.S)()
+        status = self._lib.vfem_hom_mg_solve_cells(self._h, _ptr(Wp), float(tol), int(maxIter), int(smoothing), its, res, _stream())
+        return status, list(its), list(res)
+
+
+def solveCellProblems_device(sim, tol=1e-10, maxIter=20000, preconditioner="jacobi", levels=None, smoothing=1):
     """the S fluctuation fields as one device tensor [S, numNodes, N]; see ``solveCellProblems``"""
-    global last_iterations, last_relative_residuals
+    global last_iterations, last_relative_residuals, last_levels
+    if preconditioner not in ("jacobi", "multigrid"):
+        raise ValueError("preconditioner must be \"jacobi\" or \"multigrid\" (got %r)" % (preconditioner,))
     c = _Cell(sim)
     Wp = torch.empty((c.S, c.pn, c.N), dtype=torch.float64, device=_dev())
-    its, res = (ctypes.c_int * c.S)(), (ctypes.c_double * c.S)()
-    status = _lib.load().vfem_hom_solve_cells(*c.head(), _ptr(Wp), float(tol), int(maxIter), its, res, _stream())
+    if preconditioner == "multigrid":
+        h = _Hierarchy(c, levels)
+        try:
+            status, its, res = h.solve(Wp, tol, maxIter, smoothing)
+            last_levels = [list(d) for d in h.dims]
+        finally:
+            h.close()
+    else:
+        its, res = (ctypes.c_int * c.S)(), (ctypes.c_double * c.S)()
+        status = _lib.load().vfem_hom_solve_cells(*c.head(), _ptr(Wp), float(tol), int(maxIter), its, res, _stream())
     last_iterations, last_relative_residuals = list(its), list(res)
     _lib.check(status)
     return c.to_full(Wp)
 
 
-def solveCellProblems(sim, tol=1e-10, maxIter=20000):
+def solveCellProblems(sim, tol=1e-10, maxIter=20000, preconditioner="jacobi", levels=None, smoothing=1):
     """TPPeriodicHomogenization::solveCellProblems: for every unit strain e_q the periodic fluctuation w_q with
-    K_per w_q = - sum_e E_e L[:, q], w_q = 0 at node 0, by a batched block-Jacobi PCG to ``|r| / |b| <= tol``.  Returns a list of S
+    K_per w_q = - sum_e E_e L[:, q], w_q = 0 at node 0, by a batched PCG to ``|r| / |b| <= tol``.  Returns a list of S
     arrays [numNodes, N]; raises RuntimeError when a case has not converged after ``maxIter`` iterations.  The iteration counts and
-    final residuals are left in ``last_iterations`` / ``last_relative_residuals``.  ``sim`` is not changed."""
-    return list(_to_np(solveCellProblems_device(sim, tol, maxIter)))
+    final residuals are left in ``last_iterations`` / ``last_relative_residuals``.  ``sim`` is not changed.
+
+    ``preconditioner``: ``"jacobi"`` (node blocks; the iteration count grows with the cell's extent) or ``"multigrid"``: one V-cycle
+    of a periodic geometric multigrid per iteration, with ``smoothing`` multicolour block Gauss-Seidel sweeps before and after the
+    coarse correction.  The cell is halved per level while every extent is even and at least 4, at most ``levels`` times
+    (None: as far as that goes); the last level is solved exactly, so its dofs must fit the dense coarsest-level solver
+    (RuntimeError otherwise: a large cell needs extents with enough factors of 2).  ``last_levels`` then holds the level sizes."""
+    return list(_to_np(solveCellProblems_device(sim, tol, maxIter, preconditioner, levels, smoothing)))
 
 
 def _tensor_from(D, dim):

@@ -3,6 +3,11 @@ run, so that every size runs under a time limit of its own), and the periodic ap
 is bounded by --timeout seconds (SIGALRM ends it with exit status 124).
 
     python tools/hom_time.py --n 64 [--emin 1e-3] [--tol 1e-10] [--reps 20] [--warmup 3] [--timeout 300]
+                             [--preconditioner jacobi|multigrid] [--smoothing 1]
+
+With --preconditioner multigrid the line also holds the level sizes, the time to build the hierarchy (Galerkin products, inverted
+diagonal blocks, the dense coarsest inverse; host wall time around a synchronised build, median), the device memory it holds and
+the time of one V-cycle on all S columns (HIP events, median).  The whole-solve time includes the build.
 
 The apply is timed through vfem_hom_apply (HIP events, median); that call also uploads its element tables and synchronises, so
 the same call on a 2^3 cell is timed as the fixed cost and subtracted.  Compulsory HBM traffic of one apply: read W, write W_out
@@ -67,6 +72,28 @@ def _apply_ms(sim, reps, warmup):
     return _time(lambda: _lib.check(lib.vfem_hom_apply(*c.head(), pv._ptr(w), pv._ptr(out), pv._stream())), reps, warmup), c
 
 
+def _hierarchy_figures(sim, a):
+    from ndr_amd import homogenization as hom
+    c = hom._Cell(sim)
+    build = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        h = hom._Hierarchy(c)
+        torch.cuda.synchronize()
+        build.append(time.perf_counter() - t0)
+        h.close()
+    h = hom._Hierarchy(c)
+    gen = torch.Generator("cuda").manual_seed(2)
+    B = torch.randn((c.S, c.pn, c.N), dtype=torch.float64, device="cuda", generator=gen)
+    B[:, 0] = 0.0
+    vcycle_ms = _time(lambda: h.vcycle(B, a.smoothing), a.reps, a.warmup)
+    out = {"smoothing": a.smoothing, "levels": h.dims, "hierarchy_build_seconds": round(float(np.median(build)), 4),
+           "hierarchy_bytes": h.bytes, "vcycle_ms": round(vcycle_ms, 4)}
+    h.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=64)
@@ -75,25 +102,31 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--timeout", type=int, default=300)
+    ap.add_argument("--preconditioner", choices=["jacobi", "multigrid"], default="jacobi")
+    ap.add_argument("--smoothing", type=int, default=1)
     a = ap.parse_args()
     signal.signal(signal.SIGALRM, _expire)
     signal.alarm(a.timeout)
     from ndr_amd import homogenization as hom
     sim = _cell(a.n, a.emin)
-    hom.solveCellProblems_device(_cell(4, a.emin), tol=a.tol)           # library and allocator warm
+    how = dict(preconditioner=a.preconditioner, smoothing=a.smoothing)
+    hom.solveCellProblems_device(_cell(4, a.emin), tol=a.tol, **how)    # library and allocator warm
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    W = hom.solveCellProblems_device(sim, tol=a.tol)
+    W = hom.solveCellProblems_device(sim, tol=a.tol, **how)
     torch.cuda.synchronize()
     seconds = time.perf_counter() - t0
     its = list(hom.last_iterations)
+    extra = {}
+    if a.preconditioner == "multigrid":
+        extra = _hierarchy_figures(sim, a)
     Eh = hom.homogenizedElasticityTensor_device(W, sim).D
     t_apply, c = _apply_ms(sim, a.reps, a.warmup)
     t_fixed, _ = _apply_ms(_cell(2, a.emin), a.reps, a.warmup)
     nbytes = (2 * c.S * c.N + 1) * 8 * c.pn
     kernel_ms = max(t_apply - t_fixed, 1e-6)
     print(json.dumps({
-        "tool": "hom_time", "n": a.n, "E_min": a.emin, "tol": a.tol, "void_radius": 0.3,
+        "tool": "hom_time", "n": a.n, "E_min": a.emin, "tol": a.tol, "void_radius": 0.3, "preconditioner": a.preconditioner, **extra,
         "iterations": its, "relative_residuals": list(hom.last_relative_residuals),
         "solve_seconds_all_cases": round(seconds, 4), "ms_per_iteration": round(1e3 * seconds / max(its), 4),
         "Eh_diag": [round(float(v), 6) for v in np.diag(Eh)],
