@@ -6,12 +6,19 @@
 #pragma once
 #include "vfem_internal.h"
 
+#include <functional>
+
 namespace vfem {
 
-struct HomProblem {
-    int N, S, ke;            // dimension, strain cases, dofs of an element
-    int n[3];                // elements (= periodic nodes) per axis; n[2] unused in 2-D
-    int pn;                  // periodic nodes = elements
+// a periodic node grid: the cell, or a coarse level of its multigrid hierarchy (hom_mg.h)
+struct HomGrid {
+    int N, S;                // dimension, strain cases
+    int n[3];                // periodic nodes (= elements of the cell) per axis; n[2] = 1 in 2-D
+    int pn;                  // periodic nodes
+};
+
+struct HomProblem : HomGrid {
+    int ke;                  // dofs of an element
     const double *K0;        // device, ke x ke: full-density element matrix
     const double *L;         // device, ke x S: L[:, q] = element load of the constant stress C : e_q
     const double *D;         // device, S x S: flattened tensor
@@ -56,7 +63,7 @@ void hom_setup(HomCall &c, const char *who, int dim, const int64_t *nelems, cons
                double vol, const double *E, hipStream_t s);
 
 constexpr int HOM_THREADS = 256;
-inline int hom_node_blocks(const HomProblem &p) { return (p.pn + HOM_THREADS - 1) / HOM_THREADS; }
+inline int hom_node_blocks(const HomGrid &g) { return (g.pn + HOM_THREADS - 1) / HOM_THREADS; }
 // the tensor reduction walks the elements with a grid of fixed size (a function of the cell alone: the summation order is fixed)
 inline int hom_tensor_blocks(const HomProblem &p) { const int b = hom_node_blocks(p); return b < 512 ? b : 512; }
 
@@ -67,17 +74,33 @@ void launch_hom_jacobi(const HomProblem &p, double *Minv, hipStream_t s);
 // b[s][node] = - sum over the incident elements of E_e L[(local node, .), s]; zero at the pin
 void launch_hom_rhs(const HomProblem &p, double *b, hipStream_t s);
 // alpha[s] = rz[s] / (p . Ap)[s] for the columns still active (0 for a frozen one), from the apply's block sums
-void launch_hom_finish_alpha(const HomProblem &p, const double *partial, HomState *st, hipStream_t s);
+void launch_hom_finish_alpha(const HomGrid &g, const double *partial, HomState *st, hipStream_t s);
 // x += alpha p, r -= alpha Ap, z = Minv r; partial: [2 S][node blocks] block sums of r . z and r . r
 void launch_hom_update(const HomProblem &p, const double *Minv, const double *pv, const double *Ap, double *x, double *r, double *z,
                        const HomState *st, double *partial, hipStream_t s);
 // beta[s] = rz_new / rz, rz = rz_new, rr[s]; a column with rr <= tol^2 bb is frozen.  init: rz, bb from the first residual
-void launch_hom_finish_beta(const HomProblem &p, const double *partial, HomState *st, double tol, int init, hipStream_t s);
+void launch_hom_finish_beta(const HomGrid &g, const double *partial, HomState *st, double tol, int init, hipStream_t s);
 // p = z + beta p
-void launch_hom_direction(const HomProblem &p, const double *z, double *pv, const HomState *st, hipStream_t s);
+void launch_hom_direction(const HomGrid &g, const double *z, double *pv, const HomState *st, hipStream_t s);
 // Eh[q][r] = inv_cell sum_e E_e (w_{q,e} . L[:, r] + vol D[q][r]); partial: S S hom_tensor_blocks doubles, Eh: device S S
 void launch_hom_tensor(const HomProblem &p, const double *W, double inv_cell, double *partial, double *Eh, hipStream_t s);
 // G[e][q][r] = dE[e] (1 when null) inv_cell (w_q^T K0 w_r + w_q . L[:, r] + L[:, q] . w_r + vol D[q][r]), upper triangle mirrored
 void launch_hom_gradient(const HomProblem &p, const double *W, const double *dE, double inv_cell, double *G, hipStream_t s);
+
+// The batched PCG of the cell problems (hom.hip), written once for its preconditioners.  It owns the work vectors, the right-hand
+// side, the per-column scalars, the read-backs and the error; a preconditioner is the one step that differs:
+//   x += alpha p, r -= alpha Ap (not when `first`: x = 0, r = b), z = M^-1 r, partial = [2 S][node blocks] block sums of r . z and r . r
+// `exact`: M^-1 is the inverse, so the norms are also read back after the first iteration
+struct HomPcgVectors {
+    double *x, *r, *z, *pv, *Ap, *partial;
+    HomState *st;
+};
+struct HomPreconditioner {
+    std::function<void(bool first, const HomPcgVectors &v)> step;
+    bool exact;
+};
+// W = the S solutions to |r| / |b| <= tol; throws `who`: no convergence ... after max_iter iterations (the outputs are set first)
+void hom_pcg(const HomProblem &p, const char *who, const HomPreconditioner &M, double *W, double tol, int max_iter,
+             int *iterations_out_host, double *relres_out_host, hipStream_t s);
 
 }  // namespace vfem

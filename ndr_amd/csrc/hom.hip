@@ -1,5 +1,6 @@
 // The periodic-homogenisation entry points of include/vfem.h: batched periodic apply, the cell problems by a batched
 // block-Jacobi PCG, the homogenised tensor and its density gradient.  Handle-free: every call takes the cell's element constants.
+// hom_pcg is the batched PCG itself, which hom_mg.hip runs with its V-cycle in place of block Jacobi.
 #include "hom.h"
 #include "vfem_host.h"
 
@@ -49,6 +50,56 @@ void hom_setup(HomCall &c, const char *who, int dim, const int64_t *nelems, cons
     p.stencil = c.tables.p + nk + nl + nd;
 }
 
+void hom_pcg(const HomProblem &p, const char *who, const HomPreconditioner &M, double *W, double tol, int max_iter,
+             int *iterations_out_host, double *relres_out_host, hipStream_t s) {
+    const size_t nv = (size_t) p.S * p.pn * p.N;
+    DevBuf<double> r, z, pv, Ap, partial;
+    DevBuf<HomState> st;
+    r.alloc(nv); z.alloc(nv); pv.alloc(nv); Ap.alloc(nv);
+    partial.alloc((size_t) 2 * p.S * hom_node_blocks(p));
+    st.alloc(1);
+    st.zero(s); pv.zero(s); Ap.zero(s);
+    VFEM_HIP(hipMemsetAsync(W, 0, nv * sizeof(double), s));
+    const HomPcgVectors v{W, r.p, z.p, pv.p, Ap.p, partial.p, st.p};
+    // the second half of an iteration; the first time: x = 0, r = b, z = M^-1 r, p = z
+    auto precondition = [&](bool first) {
+        M.step(first, v);
+        launch_hom_finish_beta(p, partial.p, st.p, tol, first, s);
+        launch_hom_direction(p, z.p, pv.p, st.p, s);
+    };
+    launch_hom_rhs(p, r.p, s);
+    precondition(true);
+    HomState h;
+    auto read_state = [&]() {
+        VFEM_HIP(hipMemcpyAsync(&h, st.p, sizeof(HomState), hipMemcpyDeviceToHost, s));
+        VFEM_HIP(hipStreamSynchronize(s));
+        for (int q = 0; q < p.S; ++q)
+            if (h.active[q]) return true;
+        return false;
+    };
+    bool running = read_state();
+    for (int it = 1; running && it <= max_iter; ++it) {
+        launch_hom_apply(p, pv.p, Ap.p, partial.p, s);
+        launch_hom_finish_alpha(p, partial.p, st.p, s);
+        precondition(false);
+        // the host looks at the residual norms once every 8 iterations (a frozen column no longer moves in between); an exact
+        // preconditioner is done after the first
+        if (it % 8 == 0 || it == max_iter || (it == 1 && M.exact)) running = read_state();
+    }
+    int worst = 0;
+    for (int q = 0; q < p.S; ++q) {
+        iterations_out_host[q] = h.iters[q];
+        relres_out_host[q] = h.bb[q] > 0.0 ? std::sqrt(h.rr[q] / h.bb[q]) : 0.0;
+        if (relres_out_host[q] > relres_out_host[worst]) worst = q;
+    }
+    if (running) {
+        char msg[256];
+        snprintf(msg, sizeof msg, "%s: no convergence in %d iterations: strain case %d has |r|/|b| = %.3e (tol %.3e)", who, max_iter, worst,
+                 relres_out_host[worst], tol);
+        throw Error(msg);
+    }
+}
+
 }  // namespace vfem
 
 namespace {
@@ -83,52 +134,14 @@ int vfem_hom_solve_cells(int dim, const int64_t *nelems_host, const double *K0_h
     const HomProblem &p = c.p;
     if (!W || !iterations_out_host || !relres_out_host) throw Error("vfem_hom_solve_cells: null argument");
     if (!(tol > 0.0) || max_iter < 1) throw Error("vfem_hom_solve_cells: tol must be positive and max_iter at least 1");
-    const size_t nv = (size_t) p.S * p.pn * p.N;
-    const int nb = hom_node_blocks(p);
-    DevBuf<double> r, z, pv, Ap, Minv, partial;
-    DevBuf<HomState> st;
-    r.alloc(nv); z.alloc(nv); pv.alloc(nv); Ap.alloc(nv);
+    // block Jacobi: the fused update kernel; with alpha = 0 (the zeroed state) its first call is the first preconditioning
+    DevBuf<double> Minv;
     Minv.alloc((size_t) p.pn * p.N * p.N);
-    partial.alloc((size_t) 2 * p.S * nb);
-    st.alloc(1);
-    st.zero(s); pv.zero(s); Ap.zero(s);
-    VFEM_HIP(hipMemsetAsync(W, 0, nv * sizeof(double), s));
-    // x = 0, r = b, z = Minv r, p = z: the update kernel with alpha = 0 (the zeroed state) does the first preconditioning
     launch_hom_jacobi(p, Minv.p, s);
-    launch_hom_rhs(p, r.p, s);
-    launch_hom_update(p, Minv.p, pv.p, Ap.p, W, r.p, z.p, st.p, partial.p, s);
-    launch_hom_finish_beta(p, partial.p, st.p, tol, 1, s);
-    launch_hom_direction(p, z.p, pv.p, st.p, s);
-    HomState h;
-    auto read_state = [&]() {
-        VFEM_HIP(hipMemcpyAsync(&h, st.p, sizeof(HomState), hipMemcpyDeviceToHost, s));
-        VFEM_HIP(hipStreamSynchronize(s));
-        for (int q = 0; q < p.S; ++q)
-            if (h.active[q]) return true;
-        return false;
-    };
-    bool running = read_state();
-    for (int it = 1; running && it <= max_iter; ++it) {
-        launch_hom_apply(p, pv.p, Ap.p, partial.p, s);
-        launch_hom_finish_alpha(p, partial.p, st.p, s);
-        launch_hom_update(p, Minv.p, pv.p, Ap.p, W, r.p, z.p, st.p, partial.p, s);
-        launch_hom_finish_beta(p, partial.p, st.p, tol, 0, s);
-        launch_hom_direction(p, z.p, pv.p, st.p, s);
-        // the host looks at the residual norms once every 8 iterations (a frozen column no longer moves in between)
-        if (it % 8 == 0 || it == max_iter) running = read_state();
-    }
-    int worst = 0;
-    for (int q = 0; q < p.S; ++q) {
-        iterations_out_host[q] = h.iters[q];
-        relres_out_host[q] = h.bb[q] > 0.0 ? std::sqrt(h.rr[q] / h.bb[q]) : 0.0;
-        if (relres_out_host[q] > relres_out_host[worst]) worst = q;
-    }
-    if (running) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "vfem_hom_solve_cells: no convergence in %d iterations: strain case %d has |r|/|b| = %.3e (tol %.3e)",
-                 max_iter, worst, relres_out_host[worst], tol);
-        throw Error(msg);
-    }
+    const HomPreconditioner jacobi{[&](bool, const HomPcgVectors &v) {
+        launch_hom_update(p, Minv.p, v.pv, v.Ap, v.x, v.r, v.z, v.st, v.partial, s);
+    }, false};
+    hom_pcg(p, "vfem_hom_solve_cells", jacobi, W, tol, max_iter, iterations_out_host, relres_out_host, s);
     VFEM_CATCH
 }
 

@@ -11,14 +11,6 @@
 
 namespace vfem {
 
-// a level's periodic node grid
-struct HomGrid {
-    int N, S;
-    int n[3];                // nodes per axis; n[2] unused in 2-D
-    int pn;                  // nodes
-};
-inline int hom_grid_blocks(const HomGrid &g) { return (g.pn + HOM_THREADS - 1) / HOM_THREADS; }
-
 // where a level's blocks come from: the stored array A (E null), or for level 0 hom_build_stencil's table and the moduli
 struct HomBlocks {
     const double *A_or_stencil;

@@ -2,9 +2,8 @@
 // A handle holds the hierarchy of one cell: level 0 matrix-free, Galerkin levels stored (hom_mg.h), the coarsest level as a dense
 // inverse (CoarsestSolver).  It is built once per solve; the moduli it reads at level 0 stay the caller's.
 #include "hom_mg.h"
-#include "vfem_host.h"
+#include "mg_cycle.h"
 
-#include <cmath>
 #include <memory>
 
 using namespace vfem;
@@ -63,31 +62,38 @@ void sweep(vfem_hom_mg *h, int l, double *x, const double *b, int forward, hipSt
         launch_hom_mg_sweep_colour(h->lv[l].g, h->blocks(l), h->dinv(l), forward ? k : nc - 1 - k, x, b, s);
 }
 
-void coarse_solve(vfem_hom_mg *h, const double *b, double *x, hipStream_t s) {
-    if (h->coarsest.held != CoarsestSolver::DENSE) throw Error("the coarsest level holds no dense inverse");
-    launch_hom_mg_gemv(h->lv.back().g, h->coarsest.Ainv.p, b, x, s);
-}
+// what mg_cycle::vcycle launches on a cell's hierarchy: level 0 works on the caller's X and B and on r0, a stored level on its own
+struct HomOps {
+    vfem_hom_mg *h;
+    const double *B;
+    double *X;
+    hipStream_t s;
+    int last_level() const { return h->L(); }
+    bool symmetric() const { return true; }
+    const HomGrid &g(int l) const { return h->lv[l].g; }
+    double *x(int l) const { return l == 0 ? X : h->lv[l].x.p; }
+    const double *b(int l) const { return l == 0 ? B : h->lv[l].b.p; }
+    double *r(int l) const { return l == 0 ? h->r0.p : h->lv[l].r.p; }
+    void last_level_cycle(bool) {
+        if (h->coarsest.held != CoarsestSolver::DENSE) throw Error("the coarsest level holds no dense inverse");
+        launch_hom_mg_gemv(g(h->L()), h->coarsest.Ainv.p, b(h->L()), x(h->L()), s);
+    }
+    void enforce_dirichlet(int, bool, bool) {}  // the pin is applied inside the kernels
+    void smooth(int l, int forward, int n) { for (int k = 0; k < n; ++k) sweep(h, l, x(l), b(l), forward, s); }
+    void residual(int l) { launch_hom_mg_residual(g(l), h->blocks(l), x(l), b(l), r(l), s); }
+    void restrict_residual(int l) {
+        launch_hom_mg_restrict(g(l), g(l + 1), r(l), h->lv[l + 1].b.p, s);
+        // a smoothed level starts from zero; the coarsest x is overwritten by the dense product
+        if (l + 1 < h->L()) VFEM_HIP(hipMemsetAsync(x(l + 1), 0, h->vec(l + 1) * sizeof(double), s));
+    }
+    void prolong_correction(int l) { launch_hom_mg_prolong_add(g(l), g(l + 1), x(l + 1), x(l), s); }
+};
 
 // X = V-cycle(B) from a zero initial guess: `smoothing` ascending sweeps, the coarse correction, `smoothing` descending sweeps
-void vcycle(vfem_hom_mg *h, const double *B, double *X, int smoothing, hipStream_t s) {
-    const int L = h->L();
-    if (L == 0) { coarse_solve(h, B, X, s); return; }
-    for (int l = 0; l < L; ++l) {
-        double *x = l == 0 ? X : h->lv[l].x.p;
-        const double *b = l == 0 ? B : h->lv[l].b.p;
-        double *r = l == 0 ? h->r0.p : h->lv[l].r.p;
-        VFEM_HIP(hipMemsetAsync(x, 0, h->vec(l) * sizeof(double), s));
-        for (int k = 0; k < smoothing; ++k) sweep(h, l, x, b, 1, s);
-        launch_hom_mg_residual(h->lv[l].g, h->blocks(l), x, b, r, s);
-        launch_hom_mg_restrict(h->lv[l].g, h->lv[l + 1].g, r, h->lv[l + 1].b.p, s);
-    }
-    coarse_solve(h, h->lv[L].b.p, h->lv[L].x.p, s);
-    for (int l = L - 1; l >= 0; --l) {
-        double *x = l == 0 ? X : h->lv[l].x.p;
-        const double *b = l == 0 ? B : h->lv[l].b.p;
-        launch_hom_mg_prolong_add(h->lv[l].g, h->lv[l + 1].g, h->lv[l + 1].x.p, x, s);
-        for (int k = 0; k < smoothing; ++k) sweep(h, l, x, b, 0, s);
-    }
+void cycle_from_zero(vfem_hom_mg *h, const double *B, double *X, int smoothing, hipStream_t s) {
+    if (h->L() > 0) VFEM_HIP(hipMemsetAsync(X, 0, h->vec(0) * sizeof(double), s));
+    HomOps o{h, B, X, s};
+    mg_cycle::vcycle(o, 0, smoothing, true);
 }
 
 void check_smoothing(int smoothing, const char *who) {
@@ -109,7 +115,7 @@ int vfem_hom_mg_create(vfem_hom_mg **out, int dim, const int64_t *nelems_host, c
     const HomProblem &p = h->call.p;
     const int N = p.N;
     // the levels: coarsened while every n_d is even and at least 4 (max_coarsenings < 0: as far as that allows)
-    HomGrid g{N, p.S, {p.n[0], p.n[1], N == 3 ? p.n[2] : 1}, p.pn};
+    HomGrid g = p;
     std::string sizes = dims_text(g);
     h->lv.emplace_back();
     h->lv.back().g = g;
@@ -219,7 +225,7 @@ int vfem_hom_mg_vcycle(vfem_hom_mg *h, const double *B, double *X, int smoothing
     VFEM_TRY
     if (!h || !B || !X || B == X) throw Error("vfem_hom_mg_vcycle: B and X must be two arrays");
     check_smoothing(smoothing, "vfem_hom_mg_vcycle");
-    vcycle(h, B, X, smoothing, S(stream));
+    cycle_from_zero(h, B, X, smoothing, S(stream));
     VFEM_CATCH
 }
 
@@ -231,55 +237,13 @@ int vfem_hom_mg_solve_cells(vfem_hom_mg *h, double *W, double tol, int max_iter,
     if (!(tol > 0.0) || max_iter < 1) throw Error("vfem_hom_mg_solve_cells: tol must be positive and max_iter at least 1");
     check_smoothing(smoothing, "vfem_hom_mg_solve_cells");
     const HomProblem &p = h->call.p;
-    const HomGrid &g = h->lv[0].g;
-    const size_t nv = h->vec(0);
-    const int nb = hom_node_blocks(p);
-    DevBuf<double> r, z, pv, Ap, partial;
-    DevBuf<HomState> st;
-    r.alloc(nv); z.alloc(nv); pv.alloc(nv); Ap.alloc(nv);
-    partial.alloc((size_t) 2 * p.S * nb);
-    st.alloc(1);
-    st.zero(s); pv.zero(s);
-    VFEM_HIP(hipMemsetAsync(W, 0, nv * sizeof(double), s));
-    // the loop of vfem_hom_solve_cells with z = V-cycle(r): x = 0, r = b, p = z
-    launch_hom_rhs(p, r.p, s);
-    vcycle(h, r.p, z.p, smoothing, s);
-    launch_hom_mg_dots(g, r.p, z.p, partial.p, s);
-    launch_hom_finish_beta(p, partial.p, st.p, tol, 1, s);
-    launch_hom_direction(p, z.p, pv.p, st.p, s);
-    HomState hs;
-    auto read_state = [&]() {
-        VFEM_HIP(hipMemcpyAsync(&hs, st.p, sizeof(HomState), hipMemcpyDeviceToHost, s));
-        VFEM_HIP(hipStreamSynchronize(s));
-        for (int q = 0; q < p.S; ++q)
-            if (hs.active[q]) return true;
-        return false;
-    };
-    bool running = read_state();
-    for (int it = 1; running && it <= max_iter; ++it) {
-        launch_hom_apply(p, pv.p, Ap.p, partial.p, s);
-        launch_hom_finish_alpha(p, partial.p, st.p, s);
-        launch_hom_mg_update(g, pv.p, Ap.p, W, r.p, st.p, s);
-        vcycle(h, r.p, z.p, smoothing, s);
-        launch_hom_mg_dots(g, r.p, z.p, partial.p, s);
-        launch_hom_finish_beta(p, partial.p, st.p, tol, 0, s);
-        launch_hom_direction(p, z.p, pv.p, st.p, s);
-        // the host looks at the residual norms once every 8 iterations (a frozen column no longer moves in between); a one-level
-        // hierarchy is the exact inverse and is done after the first
-        if (it % 8 == 0 || it == max_iter || (it == 1 && h->L() == 0)) running = read_state();
-    }
-    int worst = 0;
-    for (int q = 0; q < p.S; ++q) {
-        iterations_out_host[q] = hs.iters[q];
-        relres_out_host[q] = hs.bb[q] > 0.0 ? std::sqrt(hs.rr[q] / hs.bb[q]) : 0.0;
-        if (relres_out_host[q] > relres_out_host[worst]) worst = q;
-    }
-    if (running) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "vfem_hom_mg_solve_cells: no convergence in %d iterations: strain case %d has |r|/|b| = %.3e (tol %.3e)",
-                 max_iter, worst, relres_out_host[worst], tol);
-        throw Error(msg);
-    }
+    // z = V-cycle(r) on all S columns at once; a one-level hierarchy is the exact inverse
+    const HomPreconditioner multigrid{[&](bool first, const HomPcgVectors &v) {
+        if (!first) launch_hom_mg_update(p, v.pv, v.Ap, v.x, v.r, v.st, s);
+        cycle_from_zero(h, v.r, v.z, smoothing, s);
+        launch_hom_mg_dots(p, v.r, v.z, v.partial, s);
+    }, h->L() == 0};
+    hom_pcg(p, "vfem_hom_mg_solve_cells", multigrid, W, tol, max_iter, iterations_out_host, relres_out_host, s);
     VFEM_CATCH
 }
 

@@ -326,8 +326,8 @@ void launch_hom_rhs(const HomProblem &p, double *b, hipStream_t s) {
                  (k_hom_rhs<3><<<nb, HOM_T, 0, s>>>(dims_of<3>(p), p.L, p.E, b)));
 }
 
-void launch_hom_finish_alpha(const HomProblem &p, const double *partial, HomState *st, hipStream_t s) {
-    k_hom_finish_alpha<<<p.S, HOM_T, 0, s>>>(partial, hom_node_blocks(p), st);
+void launch_hom_finish_alpha(const HomGrid &g, const double *partial, HomState *st, hipStream_t s) {
+    k_hom_finish_alpha<<<g.S, HOM_T, 0, s>>>(partial, hom_node_blocks(g), st);
     VFEM_HIP(hipGetLastError());
 }
 
@@ -338,14 +338,14 @@ void launch_hom_update(const HomProblem &p, const double *Minv, const double *pv
                  (k_hom_update<3><<<nb, HOM_T, 0, s>>>(dims_of<3>(p), Minv, pv, Ap, x, r, z, st, partial)));
 }
 
-void launch_hom_finish_beta(const HomProblem &p, const double *partial, HomState *st, double tol, int init, hipStream_t s) {
-    k_hom_finish_beta<<<p.S, HOM_T, 0, s>>>(partial, hom_node_blocks(p), p.S, st, tol, init);
+void launch_hom_finish_beta(const HomGrid &g, const double *partial, HomState *st, double tol, int init, hipStream_t s) {
+    k_hom_finish_beta<<<g.S, HOM_T, 0, s>>>(partial, hom_node_blocks(g), g.S, st, tol, init);
     VFEM_HIP(hipGetLastError());
 }
 
-void launch_hom_direction(const HomProblem &p, const double *z, double *pv, const HomState *st, hipStream_t s) {
-    const long long per_column = (long long) p.pn * p.N;
-    const dim3 grid((unsigned) ((per_column + HOM_T - 1) / HOM_T), (unsigned) p.S);
+void launch_hom_direction(const HomGrid &g, const double *z, double *pv, const HomState *st, hipStream_t s) {
+    const long long per_column = (long long) g.pn * g.N;
+    const dim3 grid((unsigned) ((per_column + HOM_T - 1) / HOM_T), (unsigned) g.S);
     k_hom_direction<<<grid, HOM_T, 0, s>>>(per_column, z, pv, st);
     VFEM_HIP(hipGetLastError());
 }

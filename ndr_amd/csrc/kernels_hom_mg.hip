@@ -470,12 +470,12 @@ void launch_hom_mg_galerkin(const HomGrid &fine, const HomGrid &coarse, const Ho
 }
 
 void launch_hom_mg_dinv(const HomGrid &g, const double *A, double *Dinv, hipStream_t s) {
-    const int nb = hom_grid_blocks(g);
+    const int nb = hom_node_blocks(g);
     HOM_MG_DISPATCH(g, (k_hom_mg_dinv<2><<<nb, HOM_T, 0, s>>>(dims_of<2>(g), A, Dinv)), (k_hom_mg_dinv<3><<<nb, HOM_T, 0, s>>>(dims_of<3>(g), A, Dinv)));
 }
 
 void launch_hom_mg_apply(const HomGrid &g, const double *A, const double *w, double *out, hipStream_t s) {
-    const int nb = hom_grid_blocks(g);
+    const int nb = hom_node_blocks(g);
     const HomBlocks src{A, nullptr};
     const HomDinv none{nullptr, 0, 0};
     HOM_MG_DISPATCH(g, (k_hom_mg_level<2, MG_APPLY, HomStoredBlocks<2>><<<nb, HOM_T, 0, s>>>(dims_of<2>(g), src, none, 0, w, nullptr, out)),
@@ -483,7 +483,7 @@ void launch_hom_mg_apply(const HomGrid &g, const double *A, const double *w, dou
 }
 
 void launch_hom_mg_residual(const HomGrid &g, const HomBlocks &src, const double *x, const double *b, double *out, hipStream_t s) {
-    const int nb = hom_grid_blocks(g);
+    const int nb = hom_node_blocks(g);
     const HomDinv none{nullptr, 0, 0};
 #define ARGS(N) <<<nb, HOM_T, 0, s>>>(dims_of<N>(g), src, none, 0, x, b, out)
     if (src.E) HOM_MG_DISPATCH(g, (k_hom_mg_level<2, MG_RESIDUAL, HomFineBlocks<2>> ARGS(2)), (k_hom_mg_level<3, MG_RESIDUAL, HomFineBlocks<3>> ARGS(3)));
@@ -501,19 +501,19 @@ void launch_hom_mg_sweep_colour(const HomGrid &g, const HomBlocks &src, const Ho
 }
 
 void launch_hom_mg_restrict(const HomGrid &fine, const HomGrid &coarse, const double *vf, double *vc, hipStream_t s) {
-    const int nb = hom_grid_blocks(coarse);
+    const int nb = hom_node_blocks(coarse);
     HOM_MG_DISPATCH(fine, (k_hom_mg_restrict<2><<<nb, HOM_T, 0, s>>>(dims_of<2>(fine), dims_of<2>(coarse), vf, vc)),
                     (k_hom_mg_restrict<3><<<nb, HOM_T, 0, s>>>(dims_of<3>(fine), dims_of<3>(coarse), vf, vc)));
 }
 
 void launch_hom_mg_prolong_add(const HomGrid &fine, const HomGrid &coarse, const double *vc, double *vf, hipStream_t s) {
-    const int nb = hom_grid_blocks(fine);
+    const int nb = hom_node_blocks(fine);
     HOM_MG_DISPATCH(fine, (k_hom_mg_prolong_add<2><<<nb, HOM_T, 0, s>>>(dims_of<2>(fine), dims_of<2>(coarse), vc, vf)),
                     (k_hom_mg_prolong_add<3><<<nb, HOM_T, 0, s>>>(dims_of<3>(fine), dims_of<3>(coarse), vc, vf)));
 }
 
 void launch_hom_mg_dense(const HomGrid &g, const HomBlocks &src, double *M, hipStream_t s) {
-    const int nb = hom_grid_blocks(g);
+    const int nb = hom_node_blocks(g);
 #define ARGS(N) <<<nb, HOM_T, 0, s>>>(dims_of<N>(g), src, M)
     if (src.E) HOM_MG_DISPATCH(g, (k_hom_mg_dense<2, HomFineBlocks<2>> ARGS(2)), (k_hom_mg_dense<3, HomFineBlocks<3>> ARGS(3)));
     else HOM_MG_DISPATCH(g, (k_hom_mg_dense<2, HomStoredBlocks<2>> ARGS(2)), (k_hom_mg_dense<3, HomStoredBlocks<3>> ARGS(3)));
@@ -536,7 +536,7 @@ void launch_hom_mg_update(const HomGrid &g, const double *pv, const double *Ap, 
 }
 
 void launch_hom_mg_dots(const HomGrid &g, const double *r, const double *z, double *partial, hipStream_t s) {
-    const int nb = hom_grid_blocks(g);
+    const int nb = hom_node_blocks(g);
     HOM_MG_DISPATCH(g, (k_hom_mg_dots<2><<<nb, HOM_T, 0, s>>>(dims_of<2>(g), r, z, partial)), (k_hom_mg_dots<3><<<nb, HOM_T, 0, s>>>(dims_of<3>(g), r, z, partial)));
 }
 

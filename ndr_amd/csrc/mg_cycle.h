@@ -1,5 +1,6 @@
-// The multigrid algorithm itself, written once for the three hierarchies that run it: the trilinear one (mg.hip: TunedOps), the
-// generic one (generic.hip: GenericOps) and the slab ranks' (mg_slab.hip: DistDriver).  Host code only; control flow follows the
+// The multigrid algorithm itself, written once for the four hierarchies that run it: the trilinear one (mg.hip: TunedOps), the
+// generic one (generic.hip: GenericOps), the slab ranks' (mg_slab.hip: DistDriver) and the periodic cells' (hom_mg.hip: HomOps, the
+// V-cycle only: its PCG is batched over the strain cases, hom.hip).  Host code only; control flow follows the
 // reference's VoxelFEM/MultigridSolver.hh (MG.hh): vcycle / fullMultigrid / solve / applyPreconditionerInv 447-553,
 // preconditionedConjugateGradient 696-732.
 // An operations type `Ops` says how each step is launched (plain struct, inline members, resolved at compile time):

@@ -153,10 +153,9 @@ class _Hierarchy:
         _lib.check(self._lib.vfem_hom_mg_vcycle(self._h, _ptr(B), _ptr(out), int(smoothing), _stream()))
         return out
 
-    def solve(self, Wp, tol, maxIter, smoothing):
-        its, res = (ctypes.c_int * self.cell.S)(), (ctypes.c_double * self.cell.S)()
-        status = self._lib.vfem_hom_mg_solve_cells(self._h, _ptr(Wp), float(tol), int(maxIter), int(smoothing), its, res, _stream())
-        return status, list(its), list(res)
+    def solve(self, Wp, tol, maxIter, smoothing, its, res):
+        """the status of ``vfem_hom_mg_solve_cells``; ``its`` and ``res`` are the caller's ctypes arrays of S counts and norms"""
+        return self._lib.vfem_hom_mg_solve_cells(self._h, _ptr(Wp), float(tol), int(maxIter), int(smoothing), its, res, _stream())
 
 
 def solveCellProblems_device(sim, tol=1e-10, maxIter=20000, preconditioner="jacobi", levels=None, smoothing=1):
@@ -166,15 +165,15 @@ def solveCellProblems_device(sim, tol=1e-10, maxIter=20000, preconditioner="jaco
         raise ValueError("preconditioner must be \"jacobi\" or \"multigrid\" (got %r)" % (preconditioner,))
     c = _Cell(sim)
     Wp = torch.empty((c.S, c.pn, c.N), dtype=torch.float64, device=_dev())
+    its, res = (ctypes.c_int * c.S)(), (ctypes.c_double * c.S)()
     if preconditioner == "multigrid":
         h = _Hierarchy(c, levels)
         try:
-            status, its, res = h.solve(Wp, tol, maxIter, smoothing)
+            status = h.solve(Wp, tol, maxIter, smoothing, its, res)
             last_levels = [list(d) for d in h.dims]
         finally:
             h.close()
     else:
-        its, res = (ctypes.c_int * c.S)(), (ctypes.c_double * c.S)()
         status = _lib.load().vfem_hom_solve_cells(*c.head(), _ptr(Wp), float(tol), int(maxIter), its, res, _stream())
     last_iterations, last_relative_residuals = list(its), list(res)
     _lib.check(status)

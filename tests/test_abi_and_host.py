@@ -109,10 +109,13 @@ def test_shared_device_helpers_are_defined_once(name):
 
 @pytest.mark.parametrize("text,home", [(r"MG\.hh:301-305", ["gs_colors.h"]),                                  # the colour walk's increment rule
                                        (r"__global__[^;{}]*\bk\w*_dense_finish\s*\(", ["kernels_mg.hip"]),       # a finish kernel of a dense inverse
-                                       (r"\b40000\b", ["vfem_internal.h"] * 2)])    # DENSE_COARSEST_MAX_DOFS, and WAVE_SWEEP_MAX_NODES which is another limit
+                                       (r"\b40000\b", ["vfem_internal.h"] * 2),     # DENSE_COARSEST_MAX_DOFS, and WAVE_SWEEP_MAX_NODES which is another limit
+                                       (r"it % 8 == 0", ["hom.hip"]),                                            # the cell problems' read-back rule
+                                       (r"no convergence in %d iterations", ["hom.hip"])])                       # and their error
 def test_shared_host_rules_are_written_once(text, home):
     """the colour order of the multicolour sweep, the kernel that finishes a coarsest-level inverse and the dense solver's limit are
-    said in one file each: the four sweep launchers, the two hierarchies and the C boundary use that one"""
+    said in one file each: the four sweep launchers, the two hierarchies and the C boundary use that one; so is the batched PCG of
+    the periodic cell problems (hom_pcg), which both of its preconditioners run"""
     csrc = os.path.join(ROOT, "ndr_amd", "csrc")
     found = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))
              for _ in re.finditer(text, open(os.path.join(csrc, f)).read())]
