@@ -470,7 +470,9 @@ int vfem_adam_step(int64_t n, float *param, const float *grad, float *exp_avg, f
  * vfem_hom_apply: W_out[s] = K_per W_in[s], K_per the periodic stiffness matrix with the pin's row and column replaced by the identity.
  * vfem_hom_solve_cells: K_per w_q = - sum_e E_e L[:, q] for all S cases together by block-Jacobi PCG from w = 0; a case is frozen
  *   once |r| / |b| <= tol, the host tests convergence once every 8 iterations; error (with the worst case's residual in the message,
- *   the two output arrays filled) when a case has not converged after max_iter iterations.  Results are bit-identical run to run.
+ *   the two output arrays filled) when a case has not converged after max_iter iterations, or ("breakdown in strain case q") when
+ *   every case froze and one is short of tol because its r . z is not positive: a singular cell (a node with only zero moduli
+ *   around it, non-finite moduli); the residual reported for a case with a non-finite |b| is NaN.  Results are bit-identical run to run.
  * vfem_hom_tensor: Eh[q][r] = (1 / cell_volume) sum_e E_e (w_{q,e} . L[:, r] + vol D[q][r]) to the host (not symmetrised).
  * vfem_hom_tensor_gradient: G (device) [prod(nelems)][S][S] = dE[e] / cell_volume *
  *   (w_{q,e}^T K0 w_{r,e} + w_{q,e} . L[:, r] + L[:, q] . w_{r,e} + vol D[q][r]), upper triangle mirrored; dE (device, dE_e / drho_e)

@@ -99,7 +99,8 @@ struct HomPreconditioner {
     std::function<void(bool first, const HomPcgVectors &v)> step;
     bool exact;
 };
-// W = the S solutions to |r| / |b| <= tol; throws `who`: no convergence ... after max_iter iterations (the outputs are set first)
+// W = the S solutions to |r| / |b| <= tol; throws `who`: no convergence ... after max_iter iterations, or `who`: breakdown ... when
+// every column froze and one is short of the tolerance (r . z not positive or NaN: a singular cell); the outputs are set first
 void hom_pcg(const HomProblem &p, const char *who, const HomPreconditioner &M, double *W, double tol, int max_iter,
              int *iterations_out_host, double *relres_out_host, hipStream_t s);
 

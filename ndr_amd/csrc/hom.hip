@@ -86,16 +86,26 @@ void hom_pcg(const HomProblem &p, const char *who, const HomPreconditioner &M, d
         // preconditioner is done after the first
         if (it % 8 == 0 || it == max_iter || (it == 1 && M.exact)) running = read_state();
     }
-    int worst = 0;
+    // a column is done when its right-hand side is zero or its residual has met the tolerance; a NaN on either side is not done
+    int worst = 0, broken = -1;
     for (int q = 0; q < p.S; ++q) {
         iterations_out_host[q] = h.iters[q];
-        relres_out_host[q] = h.bb[q] > 0.0 ? std::sqrt(h.rr[q] / h.bb[q]) : 0.0;
+        relres_out_host[q] = h.bb[q] == 0.0 ? 0.0 : std::isfinite(h.bb[q]) ? std::sqrt(h.rr[q] / h.bb[q]) : std::nan("");
         if (relres_out_host[q] > relres_out_host[worst]) worst = q;
+        const bool done = h.bb[q] == 0.0 || h.rr[q] <= tol * tol * h.bb[q];
+        if (!done && broken < 0) broken = q;
     }
+    char msg[512];
     if (running) {
-        char msg[256];
         snprintf(msg, sizeof msg, "%s: no convergence in %d iterations: strain case %d has |r|/|b| = %.3e (tol %.3e)", who, max_iter, worst,
                  relres_out_host[worst], tol);
+        throw Error(msg);
+    }
+    // every column froze, one of them short of the tolerance: its r . z stopped being positive
+    if (broken >= 0) {
+        snprintf(msg, sizeof msg, "%s: breakdown in strain case %d after %d iterations: r . z = %.3e is not positive (|r|/|b| = %.3e, tol %.3e); "
+                 "the cell is singular: a node whose incident elements all have zero modulus, or non-finite moduli", who, broken,
+                 h.iters[broken], h.rz[broken], relres_out_host[broken], tol);
         throw Error(msg);
     }
 }

@@ -183,8 +183,9 @@ def solveCellProblems_device(sim, tol=1e-10, maxIter=20000, preconditioner="jaco
 def solveCellProblems(sim, tol=1e-10, maxIter=20000, preconditioner="jacobi", levels=None, smoothing=1):
     """TPPeriodicHomogenization::solveCellProblems: for every unit strain e_q the periodic fluctuation w_q with
     K_per w_q = - sum_e E_e L[:, q], w_q = 0 at node 0, by a batched PCG to ``|r| / |b| <= tol``.  Returns a list of S
-    arrays [numNodes, N]; raises RuntimeError when a case has not converged after ``maxIter`` iterations.  The iteration counts and
-    final residuals are left in ``last_iterations`` / ``last_relative_residuals``.  ``sim`` is not changed.
+    arrays [numNodes, N]; raises RuntimeError when a case has not converged after ``maxIter`` iterations.  A singular cell (a node
+    whose incident elements all have zero modulus, or non-finite moduli) raises RuntimeError "breakdown in strain case q" as well.  The
+    iteration counts and final residuals are left in ``last_iterations`` / ``last_relative_residuals``.  ``sim`` is not changed.
 
     ``preconditioner``: ``"jacobi"`` (node blocks; the iteration count grows with the cell's extent) or ``"multigrid"``: one V-cycle
     of a periodic geometric multigrid per iteration, with ``smoothing`` multicolour block Gauss-Seidel sweeps before and after the

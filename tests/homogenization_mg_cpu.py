@@ -191,20 +191,70 @@ def cell_density(name):
     return np.random.default_rng(seed).uniform(0.05, 1.0, size=ne)
 
 
-def cell_D(name):
+def kind_D(kind):
     import material_ref as mr
-    kind = CELLS[name][2]
     if kind == "aniso3":
         return mr.material_file_D(mr.ANISO_3D)
     if kind == "aniso2":
         return mr.material_file_D(mr.ANISO_2D)
-    return hc.isotropic_D(1.0, 0.3, 3)
+    return hc.isotropic_D(1.0, 0.3, int(kind[-1]))              # "iso2" / "iso3"
+
+
+def cell_D(name):
+    return kind_D(CELLS[name][2])
 
 
 def cell_reference(name):
     """the direct solution of a test cell (hc.homogenize) with the unpinned hierarchy's ingredients"""
     ne, h, _, _ = CELLS[name]
     return hc.homogenize(ne, h, cell_D(name), cell_density(name), 1.0, 1e-3, 3.0)
+
+
+# The cells of tests/test_gpu_homogenization_blocks.py, the smallest on which the device's kernels run in several 256-thread
+# workgroups and its two-stage reductions see more than 256 (512) partials: (elements, voxel edge lengths, material, seed); random
+# densities in [0.05, 1], gamma = 3, E_min = 1e-3, E_0 = 1.  Too large for a direct solve in a test: only the pieces are used.
+BLOCK_CELLS = {"2d-blocks": ((72, 64), (1.0, 0.7), "aniso2", 61), "3d-blocks": ((28, 24, 28), (1.0, 0.8, 1.3), "aniso3", 62),
+               "2d-partials": ((320, 256), (1.0, 0.7), "aniso2", 63),
+               "tensor-2d": ((520, 260), (1.0, 0.7), "aniso2", 64), "tensor-3d": ((52, 52, 52), (1.0, 0.8, 1.3), "aniso3", 65)}
+# Laminates normal to x, isotropic E = 1, nu = 0.3, gamma = 1, E_min = 0, whose strain cases need very different numbers of
+# block-Jacobi iterations: (elements, voxel edge length, density of the second half)
+LAMINATES = {"lam-2d": ((48, 6), 1.0 / 48, 0.1), "lam-3d": ((64, 4, 4), 1.0 / 64, 0.5)}
+# uniform cells of density 0.7 (a zero right-hand side up to rounding): (elements, voxel edge lengths, material)
+UNIFORM_CELLS = {"6x4x8": ((6, 4, 8), (1.0, 0.8, 1.3), "aniso3"), "8x6": ((8, 6), (1.0, 0.7), "aniso2")}
+THREADS = 256                                                    # the device's workgroup size (HOM_THREADS)
+
+
+def block_cell(name):
+    """(ne, h, D, rho, gamma, E_min) of a cell of BLOCK_CELLS, LAMINATES, UNIFORM_CELLS or of the singular cell ``void-2d``: 12 x 12 on
+    the unit square, isotropic, gamma = 1, E_min = 0, density 1 except a 4 x 4 block of zeros, so that the nine nodes inside the block
+    have no stiffness at all"""
+    if name in BLOCK_CELLS:
+        ne, h, kind, seed = BLOCK_CELLS[name]
+        return ne, h, kind_D(kind), np.random.default_rng(seed).uniform(0.05, 1.0, size=ne), 3.0, 1e-3
+    if name in LAMINATES:
+        ne, edge, second = LAMINATES[name]
+        rho = np.ones(ne)
+        rho[ne[0] // 2:] = second
+        return ne, (edge,) * len(ne), hc.isotropic_D(1.0, 0.3, len(ne)), rho, 1.0, 0.0
+    if name in UNIFORM_CELLS:
+        ne, h, kind = UNIFORM_CELLS[name]
+        return ne, h, kind_D(kind), np.full(ne, 0.7), 3.0, 1e-3
+    assert name == "void-2d"
+    rho = np.ones((12, 12))
+    rho[4:8, 4:8] = 0.0
+    return (12, 12), (1.0 / 12,) * 2, hc.isotropic_D(1.0, 0.3, 2), rho, 1.0, 0.0
+
+
+def block_problem(name):
+    """dict with ne, N, D, K0, L, vol, E, dE, K (assembled, pinned) and b of ``block_cell(name)``: everything but a solve"""
+    ne, h, D, rho, gamma, Emin = block_cell(name)
+    K0, L, vol = hc.element_constants(D, h)
+    E, dE = hc.moduli(rho, 1.0, Emin, gamma)
+    return dict(ne=ne, N=len(ne), D=D, K0=K0, L=L, vol=vol, E=E, dE=dE, K=hc.assemble(ne, K0, E), b=hc.rhs(ne, L, E))
+
+
+def workgroups(n):
+    return -(-int(n) // THREADS)
 
 
 if __name__ == "__main__":

@@ -104,3 +104,66 @@ def test_iteration_counts_of_the_void_cell(ne, lo, hi):
 
 def test_grid_independence():
     assert max(_void((128, 128))) <= max(_void((32, 32))) + 5
+
+
+def test_what_the_multi_workgroup_cells_are_for():
+    """tests/test_gpu_homogenization_blocks.py chose its cells (homogenization_mg_cpu.block_cell) as the smallest that take the device's
+    kernels past one workgroup of 256 threads and its reductions past 256 and 512 partials; that is arithmetic on the sizes, pinned
+    here together with the iteration counts that make the laminates a test of the frozen columns, and the singular block of the
+    void cell"""
+    wg, T = mg.workgroups, mg.THREADS
+    nodes = lambda n: int(np.prod(n))
+    dims = {name: mg.level_dims(mg.BLOCK_CELLS[name][0]) for name in mg.BLOCK_CELLS}
+    assert dims["2d-blocks"] == [[72, 64], [36, 32], [18, 16], [9, 8]]
+    assert dims["3d-blocks"] == [[28, 24, 28], [14, 12, 14], [7, 6, 7]]
+    assert dims["2d-partials"] == [[320, 256], [160, 128], [80, 64], [40, 32], [20, 16], [10, 8], [5, 4]]
+    assert dims["tensor-2d"] == [[520, 260], [260, 130], [130, 65]] and dims["tensor-3d"] == [[52] * 3, [26] * 3, [13] * 3]
+    # 2d-blocks: 18 workgroups of nodes; stored levels with a ragged last workgroup; a stored sweep (a quarter of the nodes per colour)
+    # in two workgroups; an odd coarsest level
+    d = dims["2d-blocks"]
+    assert nodes(d[0]) == 18 * T
+    assert [nodes(n) for n in d[1:3]] == [1152, 288] and wg(1152) == 5 and wg(288) == 2 and 288 % T != 0
+    assert nodes(d[1]) // 4 == 288 and wg(288) == 2
+    assert any(n % 2 for n in d[-1])
+    # 3d-blocks: level-0 sweep of 2352 threads per colour, a stored level of 2352 nodes, its sweep of 294 threads, the coarsest matrix
+    # from the stored blocks of 294 nodes, a gemv with 882 rows
+    d = dims["3d-blocks"]
+    assert nodes(d[0]) // 8 == 2352 and nodes(d[1]) == 2352 and wg(2352) == 10 and 2352 % T != 0
+    assert nodes(d[1]) // 8 == 294 and nodes(d[2]) == 294 and wg(294) == 2 and 3 * nodes(d[2]) == 882
+    # 2d-partials: more than 256 partials per reduction needs more than 65 536 nodes; 320 = 256 + 64
+    assert nodes(dims["2d-partials"][0]) > 65536 and wg(nodes(dims["2d-partials"][0])) == 320 > T
+    # tensor cells: more than 512 workgroups of elements, fewer than 1024: the second pass of the grid-stride loop is ragged
+    assert wg(nodes(dims["tensor-2d"][0])) == 529 and wg(nodes(dims["tensor-3d"][0])) == 550
+    assert all(512 * T < nodes(dims[name][0]) < 2 * 512 * T for name in ("tensor-2d", "tensor-3d"))
+    # every other cell of the two older device test files stays below all of this
+    assert max(nodes(c[0]) for c in mg.CELLS.values()) < 65536 and 32 ** 3 < 65536
+
+    # laminates: the restatement's block-Jacobi counts; between the first and the last real column lie at least 9 iterations, so a
+    # frozen column is read back at least once (the host reads every 8 iterations)
+    counts = {}
+    for name in mg.LAMINATES:
+        pr = mg.block_problem(name)
+        counts[name] = hc.pcg_columns(pr["K"], pr["b"], pr["N"], TOL)[1]
+        norms = np.linalg.norm(pr["b"], axis=1)
+        noise = [q for q in range(len(norms)) if norms[q] < 1e-12 * norms.max()]
+        real = [counts[name][q] for q in range(len(norms)) if q not in noise]
+        print(name, counts[name], "noise columns", noise, norms)
+        assert noise == ([] if name == "lam-2d" else [3])
+        assert max(real) - min(real) >= 9
+    assert counts == {"lam-2d": [59, 59, 76], "lam-3d": [57, 57, 57, 87, 86, 86]}
+    lam3 = mg.block_problem("lam-3d")
+    assert 0.0 < np.linalg.norm(lam3["b"][3]) < 1e-18                # rounding noise, not zero: the device must cope with either
+
+    # uniform cells: no right-hand side beyond rounding
+    for name in mg.UNIFORM_CELLS:
+        assert np.abs(mg.block_problem(name)["b"]).max() < 1e-15
+
+    # the void cell: nine nodes without stiffness, so the node blocks cannot all be inverted
+    pr = mg.block_problem("void-2d")
+    diag = pr["K"].diagonal().reshape(-1, 2)
+    assert int(np.sum(np.all(diag == 0.0, axis=1))) == 9
+    try:
+        singular = not np.all(np.isfinite(hc.block_jacobi(pr["K"], 2)))
+    except np.linalg.LinAlgError:
+        singular = True
+    assert singular
