@@ -13,9 +13,15 @@
 //   * a plane is read one phase after the wait+barrier that retires it (MI355X_MICROARCH.md, two-waves item 7).
 // A DMA piece is 16 bytes on the absolute 16-byte grid of memory: a tile row (65 nodes = 1560 B) starts on an 8-byte
 // boundary, so its image starts at the aligned address at or 8 bytes below it and the consumer adds that one-double
-// shift (a parity that depends on the row and, when a plane holds an odd number of doubles, on the plane).  Aligned
-// pieces never straddle the 16-byte-aligned end of an allocation, so nothing outside the caller's buffers is read;
-// a row image starts at node max(k0, 0) so that no address precedes the array.
+// shift (a parity that depends on the row and, when a plane holds an odd number of doubles, on the plane, and on the
+// parity of u's own address in doubles: ubase8).  Aligned pieces never straddle the 16-byte-aligned end of an
+// allocation, and the last request is clamped to the piece that holds the array's last byte (last_piece), so nothing
+// behind the caller's allocation is read; the far half of that piece may lie behind the array, and no lane consumes it
+// (apply_tile: cmax).  A row image starts at node max(k0, 0), so no request lies below the piece
+// that holds u[0].  When u itself starts 8 bytes off the 16-byte grid (a view into a larger buffer), that piece -- the
+// image of row 0 of plane 0 -- starts at u - 8: there is no clamp at the front (the marching sweep has first_piece).
+// The read stays inside the caller's allocation, because device allocations start on 256-byte boundaries and such a u
+// therefore is not the start of one, and its value is never consumed: the consumer's shift skips it.
 #include "vfem_internal.h"
 #include "device_utils.h"
 #include <type_traits>
@@ -220,6 +226,11 @@ __device__ __forceinline__ void apply_tile(const Dims &d, const DmArgs2 &dm, con
     // ---- per-thread read offsets into a slot (doubles) ----------------------------------------
     int c0 = tz - cshift, c1 = tz + 1 - cshift;
     c0 = c0 < 0 ? 0 : c0; c1 = c1 < 0 ? 0 : c1;
+    // A node column behind the row's end only meets elements outside the grid, whose modulus is 0: such a lane reads the row's last
+    // node instead.  In the last row of the last plane those columns lie behind the array: when it ends 8 bytes into a 16-byte piece
+    // (3 nn odd on an aligned u, even on a u 8 bytes off), the far half of last_piece is whatever follows the array, and 0 x NaN is NaN
+    const int cmax = d.NZ - 1 - k0u;
+    c0 = c0 > cmax ? cmax : c0; c1 = c1 > cmax ? cmax : c1;
     const int o00 = ty * ROW_D + 3 * c0, o01 = ty * ROW_D + 3 * c1;
     const int o10 = (ty + 1) * ROW_D + 3 * c0, o11 = (ty + 1) * ROW_D + 3 * c1;
     int ce = tz - cshift; ce = ce < 0 ? 0 : ce;

@@ -43,9 +43,10 @@ __device__ __forceinline__ double dsmin(double a, double b, double eps, double s
     return 0.5 * (1.0 + sign * d / sqrt(d * d + eps));
 }
 
-// a column's values at layers k0 .. k0+H-1 (0 beyond nz); vector loads when nz is even (every run then starts 16-B aligned)
-__device__ __forceinline__ void load_run(const double *__restrict__ a, long long base, int k0, int nz, double v[LG_H]) {
-    if ((nz & 1) == 0) {
+// a column's values at layers k0 .. k0+H-1 (0 beyond nz); vector loads when `vec` is set: the launcher sets it (runs_aligned16) when nz
+// is even and the array starts on a 16-byte boundary, so that every run starts on one
+__device__ __forceinline__ void load_run(const double *__restrict__ a, long long base, int k0, int nz, int vec, double v[LG_H]) {
+    if (vec) {
 #pragma unroll
         for (int t = 0; t < LG_H; t += 2) {
             if (k0 + t < nz) {
@@ -60,8 +61,8 @@ __device__ __forceinline__ void load_run(const double *__restrict__ a, long long
         for (int t = 0; t < LG_H; ++t) v[t] = k0 + t < nz ? a[base + k0 + t] : 0.0;
     }
 }
-__device__ __forceinline__ void store_run(double *__restrict__ a, long long base, int k0, int nz, const double v[LG_H]) {
-    if ((nz & 1) == 0) {
+__device__ __forceinline__ void store_run(double *__restrict__ a, long long base, int k0, int nz, int vec, const double v[LG_H]) {
+    if (vec) {
 #pragma unroll
         for (int t = 0; t < LG_H; t += 2)
             if (k0 + t < nz) *reinterpret_cast<double2 *>(a + base + k0 + t) = make_double2(v[t], v[t + 1]);
@@ -101,7 +102,7 @@ struct Region {
 
 // forward: layers k0 .. k0+H-1.  out / smax of layer k0-1 come from the previous launch.
 template <int RJ>
-__global__ void __launch_bounds__(LG_T) k_langelaar_fwd(int nx, int ny, int nz, int k0, double eps, PowP pw, double invq,
+__global__ void __launch_bounds__(LG_T) k_langelaar_fwd(int nx, int ny, int nz, int k0, int vec, double eps, PowP pw, double invq,
                                                         const double *__restrict__ in, double *__restrict__ out,
                                                         double *__restrict__ smax) {
     using R = Region<RJ>;
@@ -112,7 +113,7 @@ __global__ void __launch_bounds__(LG_T) k_langelaar_fwd(int nx, int ny, int nz, 
     const long long base = ((long long) (r.inb ? r.gi : 0) * ny + (r.inb ? r.gj : 0)) * nz;
     double v[LG_H], o[LG_H] = {}, sm[LG_H] = {};
     if (r.inb) {
-        load_run(in, base, k0, nz, v);
+        load_run(in, base, k0, nz, vec, v);
         if (k0 > 0) { double q1; pw(out[base + k0 - 1], sp[0][r.L], q1); }
     } else {
 #pragma unroll
@@ -139,15 +140,15 @@ __global__ void __launch_bounds__(LG_T) k_langelaar_fwd(int nx, int ny, int nz, 
         __syncthreads();
     }
     if (r.inb && r.core) {
-        store_run(out, base, k0, nz, o);
-        store_run(smax, base, k0, nz, sm);
+        store_run(out, base, k0, nz, vec, o);
+        store_run(smax, base, k0, nz, vec, sm);
     }
 }
 
 // backward: layers k0+H-1 down to k0.  w = lambda dsmin_dx2(vars, smax) S^(1/q-1) of layer k0+H comes from the previous
 // launch through w_in (one plane of nx ny values); this launch leaves w of layer k0 in w_out.
 template <int RJ>
-__global__ void __launch_bounds__(LG_T) k_langelaar_bwd(int nx, int ny, int nz, int k0, double eps, PowP pw, double pq,
+__global__ void __launch_bounds__(LG_T) k_langelaar_bwd(int nx, int ny, int nz, int k0, int vec, double eps, PowP pw, double pq,
                                                         const double *__restrict__ g, const double *__restrict__ vars,
                                                         const double *__restrict__ outv, const double *__restrict__ smax,
                                                         const double *__restrict__ w_in, double *__restrict__ w_out,
@@ -163,10 +164,10 @@ __global__ void __launch_bounds__(LG_T) k_langelaar_bwd(int nx, int ny, int nz, 
     const int top = min(k0 + LG_H, nz) - 1;
     double gv[LG_H], xv[LG_H], ov[LG_H], sv[LG_H], below = 0.0;
     if (r.inb) {
-        load_run(g, base, k0, nz, gv);
-        load_run(vars, base, k0, nz, xv);
-        load_run(outv, base, k0, nz, ov);
-        load_run(smax, base, k0, nz, sv);
+        load_run(g, base, k0, nz, vec, gv);
+        load_run(vars, base, k0, nz, vec, xv);
+        load_run(outv, base, k0, nz, vec, ov);
+        load_run(smax, base, k0, nz, vec, sv);
         if (k0 > 0) below = outv[base + k0 - 1];
         if (top + 1 < nz) sw[0][r.L] = w_in[plane];
     } else {
@@ -203,18 +204,26 @@ __global__ void __launch_bounds__(LG_T) k_langelaar_bwd(int nx, int ny, int nz, 
         double gr[LG_H];
 #pragma unroll
         for (int t = 0; t < LG_H; ++t) gr[t] = lam[t] * dsmin(xv[t], sv[t], eps, -1.0);
-        store_run(grad, base, k0, nz, gr);
+        store_run(grad, base, k0, nz, vec, gr);
         if (k0 > 0) w_out[plane] = wk;
     }
+}
+
+// the 16-byte path of load_run / store_run: an even nz keeps every run of a 16-byte aligned array on the 16-byte grid; an array that
+// starts 8 bytes off it (a view into a larger allocation) has every run off it, and the launch takes the scalar path for all arrays
+template <class... P>
+bool runs_aligned16(int nz, const P *...arrays) {
+    return (nz & 1) == 0 && (((reinterpret_cast<uintptr_t>(arrays) & 15u) == 0) && ...);
 }
 
 template <int RJ>
 void march(int nx, int ny, int nz, double eps, double p, double q, const double *in, double *out, double *smax, hipStream_t s) {
     using R = Region<RJ>;
+    const int vec = runs_aligned16(nz, in, out, smax) ? 1 : 0;
     const dim3 grd((nx + R::CI - 1) / R::CI, (ny + R::CJ - 1) / R::CJ);
     const PowP pw{p, p == 40.0};
     for (int k0 = 0; k0 < nz; k0 += LG_H) {
-        hipLaunchKernelGGL(k_langelaar_fwd<RJ>, grd, dim3(LG_T), 0, s, nx, ny, nz, k0, eps, pw, 1.0 / q, in, out, smax);
+        hipLaunchKernelGGL(k_langelaar_fwd<RJ>, grd, dim3(LG_T), 0, s, nx, ny, nz, k0, vec, eps, pw, 1.0 / q, in, out, smax);
         VFEM_HIP(hipGetLastError());
     }
 }
@@ -226,11 +235,12 @@ void march_back(int nx, int ny, int nz, double eps, double p, double q, const do
     const dim3 grd((nx + R::CI - 1) / R::CI, (ny + R::CJ - 1) / R::CJ);
     const PowP pw{p, p == 40.0};
     const long long plane = (long long) nx * ny;
+    const int vec = runs_aligned16(nz, g, vars, out, smax, grad) ? 1 : 0;
     int c = 0;
     for (int k0 = ((nz - 1) / LG_H) * LG_H; k0 >= 0; k0 -= LG_H, ++c) {
         const double *w_in = work + (c & 1) * plane;
         double *w_out = work + ((c + 1) & 1) * plane;
-        hipLaunchKernelGGL(k_langelaar_bwd<RJ>, grd, dim3(LG_T), 0, s, nx, ny, nz, k0, eps, pw, p / q, g, vars, out, smax,
+        hipLaunchKernelGGL(k_langelaar_bwd<RJ>, grd, dim3(LG_T), 0, s, nx, ny, nz, k0, vec, eps, pw, p / q, g, vars, out, smax,
                            w_in, w_out, grad);
         VFEM_HIP(hipGetLastError());
     }

@@ -142,7 +142,11 @@ __global__ void __launch_bounds__(64 * (gsm::CW + 1)) k_gs_march_mf0(GsMarchArgs
             dm0[t] = 8u * dbl + 8u - 8u * bit;                          // (the piece that holds the row start is the one at or below it)
             dm1[t] = 8u * dbl + 8u * bit;
         }
-        auto issueU = [&](int j) {
+        // Returns which of the lane's pieces brought a double from outside the array into LDS (bit t: the near half of piece t lies in front
+        // of the array, bit 32 + t: its far half lies behind it).  Only the pieces clamped to, or equal to, first_piece of a buffer
+        // 8 bytes off the 16-byte grid / last_piece of an array that ends 8 bytes into a piece do; patchU zeroes those doubles once
+        // they have landed: the windows of the grid's first and last node column reach over them with moduli 0, and 0 x NaN is NaN
+        auto issueU = [&](int j) -> unsigned long long {
             const int i = plane_of(j);
             const bool rel = j & 1;
             const double *buf = rel ? A.uR : A.uO;
@@ -158,21 +162,39 @@ __global__ void __launch_bounds__(64 * (gsm::CW + 1)) k_gs_march_mf0(GsMarchArgs
                 const char *pp = reinterpret_cast<const char *>(buf + 3LL * i * plane) - 32;
 #pragma unroll
                 for (int t = 0; t < U_INSTR; ++t) glds16(pp + (par0 ? dm1[t] : dm0[t]), slot + 1024 * t);
-                return;
+                return 0ull;
             }
             const double *pb = buf + 3LL * i * plane - 3;               // (the bias of ugo)
+            const char *lo = reinterpret_cast<const char *>(buf), *hi = reinterpret_cast<const char *>(buf + 3LL * d.nn);
+            unsigned long long outside = 0;
 #pragma unroll
             for (int t = 0; t < U_INSTR; ++t) {
                 const char *g = reinterpret_cast<const char *>(pb + (long long) (ugo[t] >> 1) - (long long) ((par0 + (int) (ugo[t] & 1)) & 1));
                 g = g > last ? last : (g < first ? first : g);
+                outside |= ((unsigned long long) (g < lo) << t) | ((unsigned long long) (g + 8 >= hi) << (32 + t));
                 glds16(g, slot + 1024 * t);
             }
+            return outside;
         };
-        issueU(0); issueU(1); issueU(2);
+        auto patchU = [&](int j, unsigned long long outside) {         // after the plane has landed, before the barrier that releases it
+            if (outside == 0) return;
+            double *slot = sU + (j % NU) * U_SLOT_D;
+#pragma unroll
+            for (int t = 0; t < U_INSTR; ++t) {
+                if ((outside >> t) & 1) slot[128 * t + 2 * lane] = 0.0;
+                if ((outside >> (32 + t)) & 1) slot[128 * t + 2 * lane + 1] = 0.0;
+            }
+        };
+        static_assert(U_INSTR <= 32, "one bit per piece and half");
+        const unsigned long long out0 = issueU(0);
+        unsigned long long out1 = issueU(1), out2 = issueU(2);          // of the planes 2 m + 1, 2 m + 2
         for (int m = 0; m < nsteps; ++m) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            if (m == 0) patchU(0, out0);
+            patchU(2 * m + 1, out1); patchU(2 * m + 2, out2);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                               // B0: the planes of step m have landed; step m-1 is finished
-            if (m + 1 < nsteps) { issueU(2 * m + 3); issueU(2 * m + 4); }
+            if (m + 1 < nsteps) { out1 = issueU(2 * m + 3); out2 = issueU(2 * m + 4); }
             __builtin_amdgcn_s_barrier();                               // B1
         }
         return;
