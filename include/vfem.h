@@ -385,6 +385,12 @@ int vfem_box_filter(const int64_t n_host[3], int radius, const double *in, doubl
  * their ranges, and a written layer whose neighbour layers inside the global grid are not all local (too few ghost layers). */
 int vfem_box_filter_slab(const int64_t n_local[3], int64_t x_first, int64_t nx_global, int64_t out_first, int64_t out_layers,
                          int radius, const double *in, double *out, int transpose, void *stream);
+/* The box filter on a PERIODIC grid (a homogenisation cell): out_i = (2 radius + 1)^-3 sum over the offsets in [-radius, radius]^3
+ * of in[(i + offset) mod n].  Every offset counts once, also where the window is wider than the grid and wraps onto an element
+ * again; an axis of extent 1 is therefore the identity (2-D grids).  The operator is symmetric (its own transpose: apply and
+ * backprop are the same call), translation invariant and preserves the mean.  in and out are two arrays.  Refused: a negative
+ * radius, and a window of more than 2^31 - 1 offsets. */
+int vfem_box_filter_periodic(const int64_t n_host[3], int radius, const double *in, double *out, void *stream);
 int vfem_projection(int64_t n, double beta, const double *x, double *out, void *stream);
 int vfem_projection_backprop(int64_t n, double beta, const double *g, const double *vars, double *out, void *stream);
 int vfem_oc_candidate(int64_t n, const double *x0, const double *dJ, const double *dc, double lambda, double move, double *out,
@@ -476,7 +482,12 @@ int vfem_adam_step(int64_t n, float *param, const float *grad, float *exp_avg, f
  * vfem_hom_tensor: Eh[q][r] = (1 / cell_volume) sum_e E_e (w_{q,e} . L[:, r] + vol D[q][r]) to the host (not symmetrised).
  * vfem_hom_tensor_gradient: G (device) [prod(nelems)][S][S] = dE[e] / cell_volume *
  *   (w_{q,e}^T K0 w_{r,e} + w_{q,e} . L[:, r] + L[:, q] . w_{r,e} + vol D[q][r]), upper triangle mirrored; dE (device, dE_e / drho_e)
- *   may be NULL for a factor 1.  sum_e E_e G_e (dE = NULL) = Eh at the exact solution. */
+ *   may be NULL for a factor 1.  sum_e E_e G_e (dE = NULL) = Eh at the exact solution.
+ * vfem_hom_tensor_gradient_contract: g (device) [prod(nelems)], g[e] = sum_{q,r} C_host[q][r] G[e][q][r] with the G that
+ *   vfem_hom_tensor_gradient writes for the same arguments, which is never formed: the vector-Jacobian product of the tensor (C a
+ *   weight matrix, 2 (Eh - E*) / |E*|^2, or the incoming gradient of an autograd node).  G_e is symmetric, so only (C + C^T) / 2
+ *   acts: C and C^T give the same bits, an antisymmetric C gives 0.  One thread per element, no atomics: bit-identical run to run.
+ *   Refused: a non-finite C. */
 int vfem_hom_apply(int dim, const int64_t *nelems_host, const double *K0_host, const double *L_host, const double *D_host, double vol,
                    const double *E, const double *W_in, double *W_out, void *stream);
 int vfem_hom_solve_cells(int dim, const int64_t *nelems_host, const double *K0_host, const double *L_host, const double *D_host,
@@ -487,6 +498,9 @@ int vfem_hom_tensor(int dim, const int64_t *nelems_host, const double *K0_host, 
 int vfem_hom_tensor_gradient(int dim, const int64_t *nelems_host, const double *K0_host, const double *L_host, const double *D_host,
                              double vol, const double *E, const double *W, double cell_volume, const double *dE, double *G,
                              void *stream);
+int vfem_hom_tensor_gradient_contract(int dim, const int64_t *nelems_host, const double *K0_host, const double *L_host,
+                                      const double *D_host, double vol, const double *E, const double *W, double cell_volume,
+                                      const double *dE, const double *C_host, double *g, void *stream);
 
 /* ---- multigrid-preconditioned PCG for the cell problems (DESIGN "Periodic homogenisation") ----
  * vfem_hom_mg_create builds the hierarchy of one cell from the arguments every vfem_hom_* call starts with; the handle keeps the

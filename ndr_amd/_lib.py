@@ -160,7 +160,8 @@ SIGNATURES = {
     "vfem_box_filter": (c_int, [POINTER(c_int64), c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "vfem_box_filter_slab": (c_int, [POINTER(c_int64), c_int64, c_int64, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int,
                                      c_void_p]),
-    "vfem_projection": (c_int, [c_int64, c_double, c_void_p, c_void_p, c_void_p]),
+    "vfem_box_filter_periodic": (c_int, [POINTER(c_int64), c_int, c_void_p, c_void_p, c_void_p]),
+    "vfem_projection":(c_int, [c_int64, c_double, c_void_p, c_void_p, c_void_p]),
     "vfem_projection_backprop": (c_int, [c_int64, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vfem_oc_candidate": (c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p]),
     "vfem_mean": (c_int, [c_int64, c_void_p, POINTER(c_double), c_void_p]),
@@ -182,7 +183,8 @@ SIGNATURES = {
     "vfem_hom_solve_cells": (c_int, _HOM + [c_void_p, c_double, c_int, POINTER(c_int), POINTER(c_double), c_void_p]),
     "vfem_hom_tensor": (c_int, _HOM + [c_void_p, c_double, POINTER(c_double), c_void_p]),
     "vfem_hom_tensor_gradient": (c_int, _HOM + [c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
-    "vfem_hom_mg_create": (c_int, [POINTER(c_void_p)] + _HOM + [c_int, c_void_p]),
+    "vfem_hom_tensor_gradient_contract": (c_int, _HOM + [c_void_p, c_double, c_void_p, POINTER(c_double), c_void_p, c_void_p]),
+    "vfem_hom_mg_create":(c_int, [POINTER(c_void_p)] + _HOM + [c_int, c_void_p]),
     "vfem_hom_mg_destroy": (c_int, [c_void_p]),
     "vfem_hom_mg_num_levels": (c_int, [c_void_p]),
     "vfem_hom_mg_bytes": (c_int64, [c_void_p]),

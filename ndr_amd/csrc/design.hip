@@ -43,6 +43,22 @@ int vfem_box_filter_slab(const int64_t n_local[3], int64_t x_first, int64_t nx_g
                            (int) out_layers, radius, in, out, transpose, S(stream));
     VFEM_CATCH
 }
+int vfem_box_filter_periodic(const int64_t n[3], int radius, const double *in, double *out, void *stream) {
+    VFEM_TRY
+    if (radius < 0) throw Error("negative filter radius");
+    if (!n || !in || !out || in == out) throw Error("vfem_box_filter_periodic: in and out must be two arrays");
+    for (int d = 0; d < 3; ++d)
+        if (n[d] < 1 || n[d] > (1 << 30)) throw Error("vfem_box_filter_periodic: invalid grid dimensions");
+    if (radius > (1 << 30)) throw Error("vfem_box_filter_periodic: radius too large");
+    // every offset counts, also past the grid's extent: the window is not clipped to it
+    int64_t offsets = 1;
+    for (int d = 0; d < 3; ++d) {
+        if (n[d] > 1) offsets *= 2 * (int64_t) radius + 1;
+        if (offsets > INT32_MAX) throw Error("vfem_box_filter_periodic: neighbourhood too large");
+    }
+    launch_box_filter_periodic((int) n[0], (int) n[1], (int) n[2], radius, in, out, S(stream));
+    VFEM_CATCH
+}
 int vfem_projection(int64_t n, double beta, const double *x, double *out, void *stream) {
     VFEM_TRY
     if (!(beta > 0)) throw Error("Beta parameter has to be positive (received beta = " + std::to_string(beta) + ")");

@@ -86,6 +86,9 @@ void launch_hom_direction(const HomGrid &g, const double *z, double *pv, const H
 void launch_hom_tensor(const HomProblem &p, const double *W, double inv_cell, double *partial, double *Eh, hipStream_t s);
 // G[e][q][r] = dE[e] (1 when null) inv_cell (w_q^T K0 w_r + w_q . L[:, r] + L[:, q] . w_r + vol D[q][r]), upper triangle mirrored
 void launch_hom_gradient(const HomProblem &p, const double *W, const double *dE, double inv_cell, double *G, hipStream_t s);
+// g[e] = sum_{q <= r} wt[q][r] G[e][q][r] with the G of launch_hom_gradient, which is not formed; wt: device S S, read where q <= r
+void launch_hom_gradient_contract(const HomProblem &p, const double *W, const double *dE, double inv_cell, const double *wt, double *g,
+                                  hipStream_t s);
 
 // The batched PCG of the cell problems (hom.hip), written once for its preconditioners.  It owns the work vectors, the right-hand
 // side, the per-column scalars, the read-backs and the error; a preconditioner is the one step that differs:

@@ -188,4 +188,30 @@ int vfem_hom_tensor_gradient(int dim, const int64_t *nelems_host, const double *
     VFEM_CATCH
 }
 
+int vfem_hom_tensor_gradient_contract(int dim, const int64_t *nelems_host, const double *K0_host, const double *L_host,
+                                      const double *D_host, double vol, const double *E, const double *W, double cell_volume,
+                                      const double *dE, const double *C_host, double *g, void *stream) {
+    VFEM_TRY
+    hipStream_t s = S(stream);
+    HomCall c;
+    hom_setup(c, "vfem_hom_tensor_gradient_contract", dim, nelems_host, K0_host, L_host, D_host, vol, E, s);
+    if (!W || !C_host || !g) throw Error("vfem_hom_tensor_gradient_contract: null argument");
+    const double cell = cell_volume_of(c.p, cell_volume, "vfem_hom_tensor_gradient_contract");
+    // G_e is symmetric, so only (C + C^T) / 2 acts: entry (q, r), q < r, stands for both mirrored entries
+    const int n = c.p.S;
+    std::vector<double> host((size_t) n * n, 0.0);
+    for (int q = 0; q < n; ++q)
+        for (int r = q; r < n; ++r) {
+            const double a = C_host[q * n + r], b = C_host[r * n + q];
+            if (!std::isfinite(a) || !std::isfinite(b)) throw Error("vfem_hom_tensor_gradient_contract: C is not finite");
+            host[q * n + r] = q == r ? a : a + b;
+        }
+    DevBuf<double> wt;
+    wt.alloc(host.size());
+    VFEM_HIP(hipMemcpyAsync(wt.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    launch_hom_gradient_contract(c.p, W, dE, 1.0 / cell, wt.p, g, s);
+    VFEM_HIP(hipStreamSynchronize(s));          // the tables and `host` are freed on return
+    VFEM_CATCH
+}
+
 }  // extern "C"

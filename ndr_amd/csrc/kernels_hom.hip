@@ -1,5 +1,6 @@
 // Periodic homogenisation kernels (hom.h): the batched matrix-free periodic operator, its node-block Jacobi preconditioner, the
-// vector updates and two-stage reductions of the batched PCG, the homogenised tensor and its density gradient.
+// vector updates and two-stage reductions of the batched PCG, the homogenised tensor, its density gradient and that gradient
+// contracted with a matrix.
 //
 // (The device helpers shared with the multigrid kernels are in hom_device.h.)
 // Apply: one thread owns one periodic node and gathers.  It does not walk element by element: for each of the 3^N neighbour
@@ -304,6 +305,53 @@ __global__ __launch_bounds__(HOM_T) void k_hom_gradient(HomDims<N> g, const doub
     }
 }
 
+// The gradient contracted with an S x S matrix without forming the block: gout[e] = sum_{q <= r} wt[q][r] v_qr scale, v_qr the very
+// sum k_hom_gradient stores at (q, r) and (r, q), wt[q][r] = C[q][r] + C[r][q] above the diagonal and C[q][q] on it (hom.hip).  The
+// same two rolled loops, so the same 2 KE doubles of per-thread state; a pair whose weight is zero (wave-uniform) is skipped.
+template <int N>
+__global__ __launch_bounds__(HOM_T) void k_hom_gradient_contract(HomDims<N> g, const double *__restrict__ K0, const double *__restrict__ L,
+                                                                 const double *__restrict__ D, double vol, const double *__restrict__ W,
+                                                                 const double *__restrict__ dE, double inv_cell,
+                                                                 const double *__restrict__ wt, double *__restrict__ gout) {
+    using T = HomTraits<N>;
+    constexpr int S = T::S, NPE = T::NPE, KE = T::KE;
+    const int e = blockIdx.x * HOM_T + threadIdx.x;
+    if (e >= g.pn) return;
+    int nb[N][3], nd[NPE];
+    hom_neighbours<N>(e, g, nb);
+    hom_element_nodes<N>(g, nb, nd);
+    double acc = 0.0;
+#pragma unroll 1
+    for (int r = 0; r < S; ++r) {
+        double wr[KE], y[KE];
+#pragma unroll
+        for (int m = 0; m < NPE; ++m)
+#pragma unroll
+            for (int b = 0; b < N; ++b) wr[m * N + b] = W[((long long) r * g.pn + nd[m]) * N + b];
+#pragma unroll
+        for (int i = 0; i < KE; ++i) {
+            const double *K = launder_uniform(K0);             // one row of K0 in flight at a time
+            double v = L[i * S + r];
+#pragma unroll
+            for (int j = 0; j < KE; ++j) v += K[i * KE + j] * wr[j];
+            y[i] = v;
+        }
+#pragma unroll 1
+        for (int q = 0; q <= r; ++q) {
+            const double c = wt[q * S + r];
+            if (c == 0.0) continue;
+            double v = vol * D[q * S + r];
+#pragma unroll
+            for (int m = 0; m < NPE; ++m)
+#pragma unroll
+                for (int b = 0; b < N; ++b)
+                    v += W[((long long) q * g.pn + nd[m]) * N + b] * y[m * N + b] + L[(m * N + b) * S + q] * wr[m * N + b];
+            acc += c * v;
+        }
+    }
+    gout[e] = acc * ((dE ? dE[e] : 1.0) * inv_cell);
+}
+
 }  // namespace
 
 #define HOM_DISPATCH(p, call2, call3) do { if ((p).N == 2) { call2; } else { call3; } VFEM_HIP(hipGetLastError()); } while (0)
@@ -362,6 +410,13 @@ void launch_hom_gradient(const HomProblem &p, const double *W, const double *dE,
     const int nb = hom_node_blocks(p);
     HOM_DISPATCH(p, (k_hom_gradient<2><<<nb, HOM_T, 0, s>>>(dims_of<2>(p), p.K0, p.L, p.D, p.vol, W, dE, inv_cell, G)),
                  (k_hom_gradient<3><<<nb, HOM_T, 0, s>>>(dims_of<3>(p), p.K0, p.L, p.D, p.vol, W, dE, inv_cell, G)));
+}
+
+void launch_hom_gradient_contract(const HomProblem &p, const double *W, const double *dE, double inv_cell, const double *wt, double *g,
+                                  hipStream_t s) {
+    const int nb = hom_node_blocks(p);
+    HOM_DISPATCH(p, (k_hom_gradient_contract<2><<<nb, HOM_T, 0, s>>>(dims_of<2>(p), p.K0, p.L, p.D, p.vol, W, dE, inv_cell, wt, g)),
+                 (k_hom_gradient_contract<3><<<nb, HOM_T, 0, s>>>(dims_of<3>(p), p.K0, p.L, p.D, p.vol, W, dE, inv_cell, wt, g)));
 }
 
 }  // namespace vfem

@@ -337,6 +337,36 @@ void launch_box_filter_slab(int nx, int ny, int nz, int x_first, int nx_global, 
     VFEM_HIP(hipGetLastError());
 }
 
+// box filter of radius r on a PERIODIC grid: out_i = (2r+1)^-d sum over the offsets in [-r, r]^d of in[(i + offset) mod n], d the
+// number of axes with more than one element (on an axis of extent 1 every offset is the element itself: the identity, skipped).
+// Every offset counts once, also where the window is wider than the grid and meets an element again.  Symmetric, so its own
+// transpose, and mean-preserving.  Per axis the first neighbour is wrapped by a true modulo (correct for i - r < -n), the
+// following ones by a compare; offsets ascending, axis 0 outermost, one division.
+__global__ void __launch_bounds__(256) k_box_filter_periodic(int nx, int ny, int nz, int r, const double *__restrict__ in,
+                                                             double *__restrict__ out) {
+    const long long n = (long long) nx * ny * nz;
+    const int wx = nx > 1 ? 2 * r + 1 : 1, wy = ny > 1 ? 2 * r + 1 : 1, wz = nz > 1 ? 2 * r + 1 : 1;
+    const double count = (double) ((long long) wx * wy * wz);
+    for (long long e = (long long) blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (long long) gridDim.x * blockDim.x) {
+        const int k = (int) (e % nz), j = (int) ((e / nz) % ny), i = (int) (e / ((long long) nz * ny));
+        int a0 = (i - r) % nx, b0 = (j - r) % ny, c0 = (k - r) % nz;
+        if (a0 < 0) a0 += nx;
+        if (b0 < 0) b0 += ny;
+        if (c0 < 0) c0 += nz;
+        double acc = 0.0;
+        for (int ia = 0, a = a0; ia < wx; ++ia, a = a + 1 == nx ? 0 : a + 1)
+            for (int ib = 0, b = b0; ib < wy; ++ib, b = b + 1 == ny ? 0 : b + 1) {
+                const double *row = in + ((long long) a * ny + b) * nz;
+                for (int ic = 0, c = c0; ic < wz; ++ic, c = c + 1 == nz ? 0 : c + 1) acc += row[c];
+            }
+        out[e] = acc / count;
+    }
+}
+void launch_box_filter_periodic(int nx, int ny, int nz, int r, const double *in, double *out, hipStream_t s) {
+    k_box_filter_periodic<<<grid_for((long long) nx * ny * nz, 256), 256, 0, s>>>(nx, ny, nz, r, in, out);
+    VFEM_HIP(hipGetLastError());
+}
+
 // mode 0: out = 0.5 (tanh(b/2) + tanh(b (x - 1/2))) / tanh(b/2);  mode 1: out = g * 0.5 b (1 - tanh^2(b (x - 1/2))) / tanh(b/2)
 __global__ void __launch_bounds__(256) k_projection(long long n, double beta, const double *__restrict__ x,
                                                     const double *__restrict__ g, double *__restrict__ out, int mode) {

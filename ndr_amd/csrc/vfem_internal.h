@@ -196,6 +196,7 @@ void launch_pcg_step(long long n, double *x, double *r, const double *dv, const 
 void launch_shift_scalar(double *sc, hipStream_t s);   // sc[1] = sc[0]
 
 void launch_box_filter(int nx, int ny, int nz, int r, const double *in, double *out, int transpose, hipStream_t s);
+void launch_box_filter_periodic(int nx, int ny, int nz, int r, const double *in, double *out, hipStream_t s);
 void launch_box_filter_slab(int nx, int ny, int nz, int x_first, int nx_global, int out_first, int out_layers, int r,
                             const double *in, double *out, int transpose, hipStream_t s);
 void launch_projection(long long n, double beta, const double *x, const double *g, double *out, int mode, hipStream_t s);

@@ -3,6 +3,7 @@
     w  = solveCellProblems(sim)                       # S fluctuation fields, S = 3 (2-D) or 6 (3-D)
     Eh = homogenizedElasticityTensor(w, sim)          # an ElasticityTensor: the base material of a macro-scale run
     dE = homogenizedElasticityTensorGradient(w, sim)  # [numElements, S, S]: d Eh / d rho_e
+    g  = homogenizedElasticityTensorGradientContracted(w, sim, C)   # [numElements]: d (C : Eh) / d rho_e, the blocks never formed
 
 for a degree-1 simulator in 2-D or 3-D holding any material.  The numerics run in ``libvfem.so`` (``vfem_hom_*``, include/vfem.h)
 on the PERIODIC node grid: node (i_0, ..) of the simulator's grid is the unknown (i_d mod ne_d), node 0 is pinned.  The simulator
@@ -26,7 +27,8 @@ from . import materials as _materials
 from .pyVoxelFEM import _dev, _ptr, _stream, _stress_load, _to_np
 
 __all__ = ["solveCellProblems", "solveCellProblems_device", "homogenizedElasticityTensor", "homogenizedElasticityTensor_device",
-           "homogenizedElasticityTensorGradient", "homogenizedElasticityTensorGradient_device", "closestIsotropicTensor",
+           "homogenizedElasticityTensorGradient", "homogenizedElasticityTensorGradient_device",
+           "homogenizedElasticityTensorGradientContracted", "homogenizedElasticityTensorGradientContracted_device", "closestIsotropicTensor",
            "last_iterations", "last_relative_residuals", "last_levels"]
 
 last_iterations = []             # PCG iterations of each strain case in the last solveCellProblems
@@ -160,10 +162,15 @@ class _Hierarchy:
 
 def solveCellProblems_device(sim, tol=1e-10, maxIter=20000, preconditioner="jacobi", levels=None, smoothing=1):
     """the S fluctuation fields as one device tensor [S, numNodes, N]; see ``solveCellProblems``"""
+    c = _Cell(sim)
+    return c.to_full(_solve(c, tol, maxIter, preconditioner, levels, smoothing))
+
+
+def _solve(c, tol, maxIter, preconditioner, levels, smoothing):
+    """the fields of the cell ``c`` on the periodic grid, [S, periodic nodes, N]"""
     global last_iterations, last_relative_residuals, last_levels
     if preconditioner not in ("jacobi", "multigrid"):
         raise ValueError("preconditioner must be \"jacobi\" or \"multigrid\" (got %r)" % (preconditioner,))
-    c = _Cell(sim)
     Wp = torch.empty((c.S, c.pn, c.N), dtype=torch.float64, device=_dev())
     its, res = (ctypes.c_int * c.S)(), (ctypes.c_double * c.S)()
     if preconditioner == "multigrid":
@@ -177,7 +184,7 @@ def solveCellProblems_device(sim, tol=1e-10, maxIter=20000, preconditioner="jaco
         status = _lib.load().vfem_hom_solve_cells(*c.head(), _ptr(Wp), float(tol), int(maxIter), its, res, _stream())
     last_iterations, last_relative_residuals = list(its), list(res)
     _lib.check(status)
-    return c.to_full(Wp)
+    return Wp
 
 
 def solveCellProblems(sim, tol=1e-10, maxIter=20000, preconditioner="jacobi", levels=None, smoothing=1):
@@ -201,12 +208,16 @@ def _tensor_from(D, dim):
     return t
 
 
-def homogenizedElasticityTensor_device(w, sim, baseCellVolume=0.0):
-    c = _Cell(sim)
-    Wp = c.to_periodic(w)
+def _tensor_of(c, Wp, baseCellVolume=0.0):
+    """the homogenised tensor of the periodic fields ``Wp`` of the cell ``c`` as a numpy array [S, S]"""
     Eh = np.empty((c.S, c.S))
     _lib.check(_lib.load().vfem_hom_tensor(*c.head(), _ptr(Wp), float(baseCellVolume) or c.cell_volume, _dp(Eh), _stream()))
-    return _tensor_from(Eh, c.N)
+    return Eh
+
+
+def homogenizedElasticityTensor_device(w, sim, baseCellVolume=0.0):
+    c = _Cell(sim)
+    return _tensor_from(_tensor_of(c, c.to_periodic(w), baseCellVolume), c.N)
 
 
 def homogenizedElasticityTensor(w, sim, baseCellVolume=0.0):
@@ -218,7 +229,10 @@ def homogenizedElasticityTensor(w, sim, baseCellVolume=0.0):
 
 def _gradient(w, sim, scaled):
     c = _Cell(sim)
-    Wp = c.to_periodic(w)
+    return _gradient_periodic(c, c.to_periodic(w), scaled)
+
+
+def _gradient_periodic(c, Wp, scaled):
     G = torch.empty((c.pn, c.S, c.S), dtype=torch.float64, device=_dev())
     _lib.check(_lib.load().vfem_hom_tensor_gradient(*c.head(), _ptr(Wp), c.cell_volume, _ptr(c.dE) if scaled else None, _ptr(G),
                                                     _stream()))
@@ -233,6 +247,29 @@ def homogenizedElasticityTensorGradient(w, sim):
     """TPPeriodicHomogenization::homogenizedElasticityTensorGradient: [numElements, S, S], the derivative of the homogenised tensor
     with respect to every density, dE_e/drho_e / |Y| (w_q^T K0 w_r + w_q . L[:, r] + L[:, q] . w_r + vol D[q, r]) on element e"""
     return _to_np(_gradient(np.stack([np.asarray(a, dtype=np.float64) for a in w]), sim, True))
+
+
+def _contracted(c, Wp, C):
+    """sum_qr C[q, r] dEh[q, r] / d rho_e for the periodic fields ``Wp`` of the cell ``c``: a device tensor [numElements]"""
+    C = np.ascontiguousarray(C.detach().cpu().numpy() if isinstance(C, torch.Tensor) else C, dtype=np.float64)
+    if C.shape != (c.S, c.S):
+        raise ValueError("the contracting matrix must be %d x %d (got %s)" % (c.S, c.S, "x".join(map(str, C.shape))))
+    g = torch.empty(c.pn, dtype=torch.float64, device=_dev())
+    _lib.check(_lib.load().vfem_hom_tensor_gradient_contract(*c.head(), _ptr(Wp), c.cell_volume, _ptr(c.dE), _dp(C), _ptr(g),
+                                                             _stream()))
+    return g
+
+
+def homogenizedElasticityTensorGradientContracted_device(w, sim, C):
+    c = _Cell(sim)
+    return _contracted(c, c.to_periodic(w), C)
+
+
+def homogenizedElasticityTensorGradientContracted(w, sim, C):
+    """``einsum("qr,eqr->e", C, homogenizedElasticityTensorGradient(w, sim))`` without the [numElements, S, S] array: the derivative
+    of  sum_qr C[q, r] Eh[q, r]  with respect to every density (the vector-Jacobian product of the homogenised tensor).  Only the
+    symmetric part of ``C`` acts, since every element's block is symmetric."""
+    return _to_np(homogenizedElasticityTensorGradientContracted_device(np.stack([np.asarray(a, dtype=np.float64) for a in w]), sim, C))
 
 
 def closestIsotropicTensor(C):

@@ -3,11 +3,17 @@ run, so that every size runs under a time limit of its own), and the periodic ap
 is bounded by --timeout seconds (SIGALRM ends it with exit status 124).
 
     python tools/hom_time.py --n 64 [--emin 1e-3] [--tol 1e-10] [--reps 20] [--warmup 3] [--timeout 300]
-                             [--preconditioner jacobi|multigrid] [--smoothing 1]
+                             [--preconditioner jacobi|multigrid] [--smoothing 1] [--design]
 
 With --preconditioner multigrid the line also holds the level sizes, the time to build the hierarchy (Galerkin products, inverted
 diagonal blocks, the dense coarsest inverse; host wall time around a synchronised build, median), the device memory it holds and
 the time of one V-cycle on all S columns (HIP events, median).  The whole-solve time includes the build.
+
+With --design the line holds the microstructure-design figures of the same cell instead: the contracted gradient
+(vfem_hom_tensor_gradient_contract, a dense and a bulk-modulus weight matrix) against vfem_hom_tensor_gradient followed by the einsum
+that does the same contraction, both with the fixed cost of the call on a 2^3 cell alongside (HIP events, medians), the bytes each
+writes, and one evaluation of HomogenizedTensorObjective with its gradient as a whole (solve, tensor, contracted gradient; host
+wall time around a synchronised call, median of 3).
 
 The apply is timed through vfem_hom_apply (HIP events, median); that call also uploads its element tables and synchronises, so
 the same call on a 2^3 cell is timed as the fixed cost and subtracted.  Compulsory HBM traffic of one apply: read W, write W_out
@@ -94,6 +100,45 @@ def _hierarchy_figures(sim, a):
     return out
 
 
+def _design_figures(sim, a):
+    from ndr_amd import homogenization as hom
+    from ndr_amd import microstructure as mic
+
+    def gradient_ms(cell_sim):
+        c = hom._Cell(cell_sim)
+        gen = torch.Generator("cuda").manual_seed(3)
+        Wp = torch.randn((c.S, c.pn, c.N), dtype=torch.float64, device="cuda", generator=gen)
+        dense = np.random.default_rng(4).standard_normal((c.S, c.S))
+        bulk = np.zeros((c.S, c.S))
+        bulk[:3, :3] = 1.0
+        Cd = torch.from_numpy(dense).cuda()
+        full = lambda: hom._gradient_periodic(c, Wp, True)
+        return {"contracted_dense_ms": _time(lambda: hom._contracted(c, Wp, dense), a.reps, a.warmup),
+                "contracted_bulk_ms": _time(lambda: hom._contracted(c, Wp, bulk), a.reps, a.warmup),
+                "blocks_ms": _time(full, a.reps, a.warmup),
+                "blocks_then_einsum_ms": _time(lambda: torch.einsum("qr,eqr->e", Cd, full()), a.reps, a.warmup)}, c
+
+    big, c = gradient_ms(sim)
+    small, _ = gradient_ms(_cell(2, a.emin))
+    obj = mic.HomogenizedTensorObjective(sim, np.pad(np.ones((3, 3)), (0, 3)), tol=a.tol, preconditioner=a.preconditioner,
+                                         smoothing=a.smoothing, skipSolve=True)
+    whole = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        obj.updateCache(None)
+        J = obj.evaluate()
+        g = obj.gradient_device()
+        torch.cuda.synchronize()
+        whole.append(time.perf_counter() - t0)
+    out = {k: round(v, 4) for k, v in big.items()}
+    out.update({"fixed_cost_" + k: round(v, 4) for k, v in small.items()})
+    out.update({"contracted_bytes_written": 8 * c.pn, "blocks_bytes_written": 8 * c.S * c.S * c.pn,
+                "objective_and_gradient_seconds": round(float(np.median(whole)), 4), "iterations": list(hom.last_iterations),
+                "J": J, "gradient_max": float(g.abs().max()), "gradient_nowhere_positive": bool((g <= 0).all())})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=64)
@@ -104,6 +149,7 @@ def main():
     ap.add_argument("--timeout", type=int, default=300)
     ap.add_argument("--preconditioner", choices=["jacobi", "multigrid"], default="jacobi")
     ap.add_argument("--smoothing", type=int, default=1)
+    ap.add_argument("--design", action="store_true")
     a = ap.parse_args()
     signal.signal(signal.SIGALRM, _expire)
     signal.alarm(a.timeout)
@@ -111,6 +157,10 @@ def main():
     sim = _cell(a.n, a.emin)
     how = dict(preconditioner=a.preconditioner, smoothing=a.smoothing)
     hom.solveCellProblems_device(_cell(4, a.emin), tol=a.tol, **how)    # library and allocator warm
+    if a.design:
+        print(json.dumps({"tool": "hom_time", "mode": "design", "n": a.n, "E_min": a.emin, "tol": a.tol, "void_radius": 0.3,
+                          "preconditioner": a.preconditioner, **_design_figures(sim, a)}), flush=True)
+        return
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     W = hom.solveCellProblems_device(sim, tol=a.tol, **how)
