@@ -534,6 +534,37 @@ int vfem_hom_mg_vcycle(vfem_hom_mg *h, const double *B, double *X, int smoothing
 int vfem_hom_mg_solve_cells(vfem_hom_mg *h, double *W, double tol, int max_iter, int smoothing, int *iterations_out_host,
                             double *relres_out_host, void *stream);
 
+/* ---- element stresses of a degree-1 grid: field, p-norm measure, adjoint load, density gradient ----
+ * Handle-free, dim = 2 (plane stress) or 3.  Every grid entry point starts with
+ *   nelems_host[dim]   elements per axis (>= 1 each), last axis fastest; the node grid has nelems + 1 nodes per axis
+ *   h_host[dim]        the voxel's edge lengths (> 0)
+ *   D_host [S][S]      flattened tensor, S = 3 (xx yy xy) or 6 (xx yy zz yz xz xy), TENSOR components (shear columns count twice)
+ * u, a, lambda (device) are [nodes][dim]; m, dm, dE, vm, g (device) are [elements]; strain, stress (device) are [elements][S].
+ * Device pointers need 8-byte alignment only.  Element e with nodal values u_e:
+ *   eps_e = mean over the element of sym(grad u) (TensorProductSimulator::elementStrain, the strain at the centroid),
+ *   sigma_e = m[e] C : eps_e, vm_e = von Mises stress of sigma_e (2-D: sqrt(sxx^2 - sxx syy + syy^2 + 3 sxy^2)).
+ * vfem_stress_fields: writes whichever of strain, stress, vm is not NULL (at least one); m may be NULL when only strain is asked for.
+ * vfem_stress_pnorm: J = (sum_i vm[i]^P)^(1/P) over n values, computed as vmax (sum (vm / vmax)^P)^(1/P) so that it cannot
+ *   overflow; J = 0 when vmax = 0.  J and (unless NULL) vmax go to the host.  Fixed summation order: bit-identical run to run.
+ * vfem_stress_adjoint_load: a = dJ/du at fixed m: a[node j] = sum over the incident elements of
+ *   (vm_e / J)^(P-1) m_e Bbar_j^T (C : dvm/dsigma at sigma_e), 0 where vm_e = 0, and 0 at the components the mask fixes (mask, device,
+ *   1 byte per node, bit c = component c; may be NULL).  J is the measure of the same u, m, P (J = 0: a = 0).  work (device) is
+ *   [elements][S] doubles of scratch: an element kernel leaves there what each element sends to its nodes, then one thread per node
+ *   gathers from its incident elements in a fixed order.  No atomics: bit-identical run to run.
+ * vfem_stress_pnorm_gradient: g[e] = (vm_e / J)^(P-1) dm[e] vm_e / m_e - dE[e] lambda_e^T K0 u_e: the derivative of J with respect
+ *   to a design variable rho_e with dm = dm/drho, dE = d(stiffness modulus)/drho, lambda the solution of K lambda = a, K0_host
+ *   [ke][ke] the full-density element matrix (ke = dim 2^dim, dof = dim node + component).
+ * Refused before any device call: NULL pointers, dim not 2 or 3, extents < 1, h <= 0, non-finite D or K0, a non-finite P or P < 1,
+ * a negative or non-finite J. */
+int vfem_stress_fields(int dim, const int64_t *nelems_host, const double *h_host, const double *D_host, const double *m,
+                       const double *u, double *strain, double *stress, double *vm, void *stream);
+int vfem_stress_pnorm(int64_t n, const double *vm, double P, double *J_host, double *vmax_host, void *stream);
+int vfem_stress_adjoint_load(int dim, const int64_t *nelems_host, const double *h_host, const double *D_host, const double *m,
+                             const double *u, double J, double P, const uint8_t *mask, double *work, double *a, void *stream);
+int vfem_stress_pnorm_gradient(int dim, const int64_t *nelems_host, const double *h_host, const double *D_host, const double *K0_host,
+                               const double *m, const double *dm, const double *dE, const double *u, const double *lambda, double J,
+                               double P, double *g, void *stream);
+
 /* ---- timers: BENCHMARK_* registry (MeshFEM GlobalBenchmark.hh / Timer.hh; VoxelFEM.cc:245-255) ---- */
 int vfem_timers_reset(void);
 int vfem_timers_report(char *buf_host, size_t buf_len);

@@ -29,6 +29,9 @@ class _DL(ctypes.Structure):
 # what every vfem_hom_* entry point starts with: dim, nelems, K0, L, D (host), vol, moduli (device)
 _HOM = [c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double), POINTER(c_double), c_double, c_void_p]
 
+# what every vfem_stress_* grid entry point starts with: dim, nelems, h, D (host)
+_STRESS = [c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]
+
 # name -> (restype, argtypes); kept in one table so tests can check it against include/vfem.h
 SIGNATURES = {
     "vfem_last_error": (c_char_p, []),
@@ -195,6 +198,11 @@ SIGNATURES = {
     "vfem_hom_mg_prolong_add": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "vfem_hom_mg_vcycle": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "vfem_hom_mg_solve_cells": (c_int, [c_void_p, c_void_p, c_double, c_int, c_int, POINTER(c_int), POINTER(c_double), c_void_p]),
+    "vfem_stress_fields": (c_int, _STRESS + [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vfem_stress_pnorm": (c_int, [c_int64, c_void_p, c_double, POINTER(c_double), POINTER(c_double), c_void_p]),
+    "vfem_stress_adjoint_load": (c_int, _STRESS + [c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vfem_stress_pnorm_gradient": (c_int, _STRESS + [POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
+                                                     c_double, c_void_p, c_void_p]),
     "vfem_timers_reset": (c_int, []),
     "vfem_timers_report": (c_int, [c_char_p, c_size_t]),
 }
