@@ -565,6 +565,37 @@ int vfem_stress_pnorm_gradient(int dim, const int64_t *nelems_host, const double
                                const double *m, const double *dm, const double *dE, const double *u, const double *lambda, double J,
                                double P, double *g, void *stream);
 
+/* ---- Method of Moving Asymptotes (Svanberg 1987 / 2007 with a_i = 0, d_i = 1, c_i = c) ----
+ * min f_0(x) subject to f_i(x) <= 0, i = 1 .. m (1 <= m <= 8), xmin <= x <= xmax, one convex separable subproblem per step.
+ * x, L, U, xmin, xmax, g0, xnew (device) are [n]; g (device) is [m][n], row i the gradient of f_i; f, b, lambda, y and the outputs
+ * of the dual evaluation are host arrays of m (hess: m x m row-major).  Device pointers need 8-byte alignment only (16-byte
+ * aligned buffers are read 16 bytes per lane).  With xm = max(xmax - xmin, 1e-5), per variable and per gradient g:
+ *   p = (U - x)^2 (1.001 g+ + 0.001 g- + 1e-5 / xm),  q = (x - L)^2 (0.001 g+ + 1.001 g- + 1e-5 / xm),
+ *   alpha = max(xmin, L + 0.1 (x - L), x - move xm),  beta = min(xmax, U - 0.1 (U - x), x + move xm),
+ *   x_j(lambda) = clamp((sqrt(P) L + sqrt(Q) U) / (sqrt(P) + sqrt(Q)), alpha, beta),  P = p_0 + lambda . p,  Q = q_0 + lambda . q,
+ *   y_i = max(0, lambda_i - c),  b_i = sum_j (p_ij / (U - x) + q_ij / (x - L)) - f_i.
+ * vfem_mma_asymptotes: L, U in place for step `iter` (from 1).  Steps 1 and 2: x -+ asyinit xm.  Later, with
+ *   s = (x - xold1)(xold1 - xold2) and the factor asyincr (s > 0), asydecr (s < 0) or 1: L = x - factor (xold1 - L), kept within
+ *   [x - 10 xm, x - 0.01 xm]; U mirrored.  xold1, xold2 may be NULL in steps 1 and 2.
+ * vfem_mma_dual_eval: one fused pass at lambda >= 0.  W = sum_j (P / (U - x_j) + Q / (x_j - L)) - lambda . b - 0.5 sum y_i^2,
+ *   grad_i = dW/dlambda_i = G_i - b_i - y_i with G_i = sum_j (p_ij / (U - x_j) + q_ij / (x_j - L)),  scale_i = G_i + |b_i| + y_i,
+ *   hess = -d2W/dlambda2 = sum over the j strictly inside (alpha, beta) of h_ij h_kj / psi''_j, plus 1 on the diagonal where
+ *   lambda_i > c.  Fixed summation order, no atomics: bit-identical run to run.
+ * vfem_mma_subproblem: computes b from f (host, the values f_i(x)), maximises W over lambda >= 0 and writes xnew = x(lambda).
+ *   It stops when max_i |r_i| <= tol scale_i, r_i = grad_i where lambda_i > 0, else max(grad_i, 0); if max_iter Newton iterations
+ *   do not get there it fails and names the residual.  lambda_out [m] is required; y_out [m], iters_out, residual_out (the largest
+ *   |r_i| / scale_i) may be NULL.
+ * Refused before any device call: n < 1, m outside 1 .. 8, NULL pointers, move <= 0, asyinit <= 0, asydecr outside (0, 1),
+ * asyincr < 1, tol <= 0, max_iter < 1, c < 0, a negative or non-finite lambda, a non-finite f or b, and an xnew that overlaps an input. */
+int vfem_mma_asymptotes(int64_t n, int iter, const double *x, const double *xold1, const double *xold2, const double *xmin,
+                        const double *xmax, double asyinit, double asyincr, double asydecr, double *L, double *U, void *stream);
+int vfem_mma_dual_eval(int64_t n, int m, const double *x, const double *L, const double *U, const double *xmin, const double *xmax,
+                       double move, const double *g0, const double *g, const double *b_host, double c, const double *lambda_host,
+                       double *W_host, double *grad_host, double *scale_host, double *hess_host, void *stream);
+int vfem_mma_subproblem(int64_t n, int m, const double *x, const double *L, const double *U, const double *xmin, const double *xmax,
+                        double move, const double *f_host, const double *g0, const double *g, double c, double tol, int max_iter,
+                        double *xnew, double *lambda_out, double *y_out, int *iters_out, double *residual_out, void *stream);
+
 /* ---- timers: BENCHMARK_* registry (MeshFEM GlobalBenchmark.hh / Timer.hh; VoxelFEM.cc:245-255) ---- */
 int vfem_timers_reset(void);
 int vfem_timers_report(char *buf_host, size_t buf_len);

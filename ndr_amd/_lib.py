@@ -203,6 +203,13 @@ SIGNATURES = {
     "vfem_stress_adjoint_load": (c_int, _STRESS + [c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vfem_stress_pnorm_gradient": (c_int, _STRESS + [POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
                                                      c_double, c_void_p, c_void_p]),
+    "vfem_mma_asymptotes": (c_int, [c_int64, c_int] + [c_void_p] * 5 + [c_double] * 3 + [c_void_p] * 3),
+    "vfem_mma_dual_eval": (c_int, [c_int64, c_int] + [c_void_p] * 5 + [c_double, c_void_p, c_void_p, POINTER(c_double), c_double,
+                                                                   POINTER(c_double), POINTER(c_double), POINTER(c_double),
+                                                                   POINTER(c_double), POINTER(c_double), c_void_p]),
+    "vfem_mma_subproblem": (c_int, [c_int64, c_int] + [c_void_p] * 5 + [c_double, POINTER(c_double), c_void_p, c_void_p, c_double,
+                                                                    c_double, c_int, c_void_p, POINTER(c_double), POINTER(c_double),
+                                                                    POINTER(c_int), POINTER(c_double), c_void_p]),
     "vfem_timers_reset": (c_int, []),
     "vfem_timers_report": (c_int, [c_char_p, c_size_t]),
 }

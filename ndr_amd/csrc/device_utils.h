@@ -110,4 +110,23 @@ __device__ __forceinline__ void gs_solve(const double bms[3], const double M[9],
 }
 
 
+// The reductions of the vector kernels (kernels_vec.hip) and of the MMA dual pass (kernels_mma.hip): the 64 lanes of a wave by
+// shuffles, lane 0 holds the sum; then the four waves of a 256-thread block through sh[4], added in order, valid in thread 0.
+// A fixed order: the same bits run to run.
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    return v;
+}
+
+__device__ __forceinline__ double block_sum_256(double v, double *sh) {
+    v = wave_sum(v);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) sh[w] = v;
+    __syncthreads();
+    double t = 0.0;
+    if (threadIdx.x == 0) t = sh[0] + sh[1] + sh[2] + sh[3];
+    return t;   // valid in thread 0
+}
+
 }  // namespace vfem

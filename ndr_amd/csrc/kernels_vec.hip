@@ -1,6 +1,7 @@
 // Elementwise / reduction kernels: SIMP moduli, Dirichlet masking, CG vector updates with
 // wavefront (64-lane) reductions, compliance sensitivity.
 #include "vfem_internal.h"
+#include "device_utils.h"
 
 #include <cstdlib>
 #include <string>
@@ -71,25 +72,9 @@ void launch_enforce_dirichlet(long long nn, const uint8_t *mask, const double *v
 }
 
 // ------------------------------------------------------------------------------------------
-// dot product: 1024 blocks of per-wave shuffle reductions -> partials -> one final block.
-// Deterministic (fixed partition and order), unlike an atomic finish.
+// dot product: 1024 blocks of per-wave shuffle reductions (wave_sum / block_sum_256, device_utils.h) -> partials -> one final
+// block.  Deterministic (fixed partition and order), unlike an atomic finish.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    return v;
-}
-
-__device__ __forceinline__ double block_sum_256(double v, double *sh) {
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) sh[w] = v;
-    __syncthreads();
-    double t = 0.0;
-    if (threadIdx.x == 0) t = sh[0] + sh[1] + sh[2] + sh[3];
-    return t;   // valid in thread 0
-}
-
 constexpr int DOT_BLOCKS = 1024;
 
 // The element loops of the PCG vector kernels take two consecutive doubles per thread and step -- one 16-byte access where the

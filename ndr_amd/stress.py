@@ -135,8 +135,9 @@ class PNormStressObjective:
     nowhere positive, which compliance has and this measure has not: adding material lowers the stress here and raises it there
     (the second term has either sign).  On a 6 x 4 cantilever with random densities 8 entries are positive and 16 negative
     (tests/test_stress_cpu.py).
-    Minimise it with a gradient method: ``gradient()`` with any optimiser, or ``pNormStress`` / ``complianceAndPNormStress`` with a
-    torch optimiser or the MLP density field."""
+    Minimise it, or cap it, with ``ndr_amd.mma.MMAOptimizer``, which takes gradients of either sign (as a constraint:
+    ``mma.ObjectiveConstraint(objective, upperBound)``), or use ``pNormStress`` / ``complianceAndPNormStress`` with a torch optimiser
+    or the MLP density field."""
 
     def __init__(self, solved, P=8.0, stressExponent=0.5):
         P = float(P)
