@@ -596,6 +596,36 @@ int vfem_mma_subproblem(int64_t n, int m, const double *x, const double *L, cons
                         double move, const double *f_host, const double *g0, const double *g, double c, double tol, int max_iter,
                         double *xnew, double *lambda_out, double *y_out, int *iters_out, double *residual_out, void *stream);
 
+/* ---- natural frequencies of a degree-1 grid: mass operator, block operations, density gradient ----
+ * Handle-free, dim = 2 or 3.  Every grid entry point starts with nelems_host[dim] and h_host[dim] as the element-stress section
+ * has them.  A block of vectors (device) is [column][node][dim]: every column is a vector of the simulators; for the two block
+ * operations a block is [column][n].  m, dE, dm, g (device) are [elements].  Device pointers need 8-byte alignment only.
+ * The consistent mass matrix of a unit-density voxel, M0, is the tensor product of the 1-D h_d / 6 [[2, 1], [1, 2]], the identity
+ * across components;  M(m) = sum_e m[e] M0;  P zeroes the components a node mask fixes (mask, device, 1 byte per node, bit c =
+ * component c; may be NULL: P = I).
+ * vfem_modal_mass_apply: Y_c = P M(m) P X_c for the ncols (1 .. 24) columns; one thread per node reads its multipliers once for
+ *   all columns.  Y must not overlap X.
+ * vfem_modal_project: X_c = P X_c in place.
+ * vfem_block_gram: G = A^T B (ka x kb row-major, ka, kb in 1 .. 24) of the blocks A [ka][n], B [kb][n], by per-workgroup partials
+ *   and one finishing kernel.  G (device) and G_host may each be NULL, not both: with G_host the matrix is copied to the host and
+ *   the stream is synchronised, without it the call is asynchronous.
+ * vfem_block_combine: B_j = sum_i C_host[i][j] A_i, i ascending, for A [kin][n], B [kout][n], C_host kin x kout row-major (kin,
+ *   kout in 1 .. 24).  B must not overlap A.  Asynchronous.
+ * vfem_modal_gradient: g[e] = sum_i (cK_host[i] dE[e] phi_ie^T K0 phi_ie + cM_host[i] dm[e] phi_ie^T M0 phi_ie) over the nmodes
+ *   (1 .. 8) columns of Phi; K0_host [ke][ke] as in vfem_stress_pnorm_gradient.
+ * No atomics, fixed summation order: results are bit-identical run to run.
+ * Refused before any device call: NULL pointers (but mask), dim not 2 or 3, extents < 1, h <= 0, a column count out of range,
+ * n < 1, non-finite coefficients or K0, and an output that overlaps an input. */
+int vfem_modal_mass_apply(int dim, const int64_t *nelems_host, const double *h_host, const double *m, const uint8_t *mask, int ncols,
+                          const double *X, double *Y, void *stream);
+int vfem_modal_project(int dim, const int64_t *nelems_host, const double *h_host, const uint8_t *mask, int ncols, double *X,
+                       void *stream);
+int vfem_block_gram(int64_t n, int ka, const double *A, int kb, const double *B, double *G, double *G_host, void *stream);
+int vfem_block_combine(int64_t n, int kin, int kout, const double *A, const double *C_host, double *B, void *stream);
+int vfem_modal_gradient(int dim, const int64_t *nelems_host, const double *h_host, int nmodes, const double *K0_host,
+                        const double *cK_host, const double *cM_host, const double *dE, const double *dm, const double *Phi, double *g,
+                        void *stream);
+
 /* ---- timers: BENCHMARK_* registry (MeshFEM GlobalBenchmark.hh / Timer.hh; VoxelFEM.cc:245-255) ---- */
 int vfem_timers_reset(void);
 int vfem_timers_report(char *buf_host, size_t buf_len);

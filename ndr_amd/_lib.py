@@ -32,6 +32,9 @@ _HOM = [c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double), POINTER(c
 # what every vfem_stress_* grid entry point starts with: dim, nelems, h, D (host)
 _STRESS = [c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]
 
+# what every vfem_modal_* grid entry point starts with: dim, nelems, h (host)
+_MODAL = [c_int, POINTER(c_int64), POINTER(c_double)]
+
 # name -> (restype, argtypes); kept in one table so tests can check it against include/vfem.h
 SIGNATURES = {
     "vfem_last_error": (c_char_p, []),
@@ -210,6 +213,12 @@ SIGNATURES = {
     "vfem_mma_subproblem": (c_int, [c_int64, c_int] + [c_void_p] * 5 + [c_double, POINTER(c_double), c_void_p, c_void_p, c_double,
                                                                     c_double, c_int, c_void_p, POINTER(c_double), POINTER(c_double),
                                                                     POINTER(c_int), POINTER(c_double), c_void_p]),
+    "vfem_modal_mass_apply": (c_int, _MODAL + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "vfem_modal_project": (c_int, _MODAL + [c_void_p, c_int, c_void_p, c_void_p]),
+    "vfem_block_gram": (c_int, [c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_double), c_void_p]),
+    "vfem_block_combine": (c_int, [c_int64, c_int, c_int, c_void_p, POINTER(c_double), c_void_p, c_void_p]),
+    "vfem_modal_gradient": (c_int, _MODAL + [c_int, POINTER(c_double), POINTER(c_double), POINTER(c_double), c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p]),
     "vfem_timers_reset": (c_int, []),
     "vfem_timers_report": (c_int, [c_char_p, c_size_t]),
 }

@@ -1,7 +1,7 @@
 // Element stresses of a degree-1 grid (stress.h): the strain / stress / von Mises field, the p-norm measure, its
 // adjoint load and its density gradient.
 //
-// Thread mapping (the one of k_compliance_gradient): a block is 64 lanes along the last (fastest) axis by 4 rows of the axis before
+// Thread mapping (cell_threads.h): a block is 64 lanes along the last (fastest) axis by 4 rows of the axis before
 // it; in 3-D blockIdx.z walks axis 0.  The field and gradient kernels give one thread to an element; the adjoint load is an element
 // kernel that stores S doubles per element and a kernel with one thread per NODE, which gathers from its up to 2^N incident elements
 // in ascending local-node order: no atomics, bit-identical run to run.  An element's strain comes from the 2^N nodal values of u:
@@ -12,6 +12,7 @@
 // where the launcher found the arrays aligned (VEC); a 3-D node is 24 bytes, loaded as three doubles.
 #include "stress.h"
 
+#include "cell_threads.h"
 #include "device_utils.h"
 
 namespace vfem {
@@ -24,30 +25,6 @@ struct StressTraits {
     static constexpr int NPE = 1 << N;
     static constexpr int KE = N * NPE;
 };
-
-// position (0 / 1) along axis d of local node a: axis 0 is the most significant bit
-template <int N>
-__device__ __forceinline__ constexpr int node_bit(int a, int d) { return (a >> (N - 1 - d)) & 1; }
-
-// the thread's cell of a grid with `ext[d] + extra` cells per axis; false: outside
-template <int N>
-__device__ __forceinline__ bool thread_cell(const int *ext, int extra, int (&c)[N]) {
-    c[N - 1] = blockIdx.x * 64 + threadIdx.x;
-    c[N - 2] = blockIdx.y * 4 + threadIdx.y;
-    if constexpr (N == 3) c[0] = blockIdx.z;
-    bool in = true;
-#pragma unroll
-    for (int d = 0; d < N; ++d) in = in && c[d] < ext[d] + extra;
-    return in;
-}
-
-template <int N>
-__device__ __forceinline__ long long flat_index(const int *ext, int extra, const int (&c)[N]) {
-    long long f = c[0];
-#pragma unroll
-    for (int d = 1; d < N; ++d) f = f * (ext[d] + extra) + c[d];
-    return f;
-}
 
 // the N components of the 2^N nodes of element ec
 template <int N, bool VEC>
@@ -340,19 +317,14 @@ __global__ void __launch_bounds__(256) k_stress_gradient(StressProblem p, const 
     g[e] = w * dm[e] * vm0 - dE[e] * en;
 }
 
-dim3 cell_grid(const StressProblem &p, int extra) {
-    const int N = p.N;
-    const dim3 grd((unsigned) (p.ne[N - 1] + extra + 63) / 64, (unsigned) (p.ne[N - 2] + extra + 3) / 4, N == 3 ? (unsigned) (p.ne[0] + extra) : 1u);
-    if (grd.y > 65535u || grd.z > 65535u) throw Error("stress kernels: grid too large along an outer axis");
-    return grd;
-}
+dim3 cell_grid(const StressProblem &p, int extra) { return vfem::cell_grid(p.N, p.ne, extra); }
 
 bool aligned16(const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
 
 // whole-number exponent of weight_power, or -1
 int whole_exponent(double pm1) { return pm1 >= 0.0 && pm1 <= 1024.0 && pm1 == (double) (int) pm1 ? (int) pm1 : -1; }
 
-const dim3 STRESS_BLOCK(64, 4, 1);
+const dim3 STRESS_BLOCK = cell_block();
 
 }  // namespace
 

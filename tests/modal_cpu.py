@@ -1,0 +1,183 @@
+"""numpy / scipy fp64 restatement of the natural-frequency chain, for the tests.  Nothing here comes from the library: K and M are
+assembled by scipy on the full node grid (stress_cpu.assemble, the element matrices of homogenization_cpu and of ``mass_element``
+here), reduced to the free dofs and solved densely by ``scipy.linalg.eigh(K, M)``; ``lobpcg`` is a plain LOBPCG with the basis
+handling of ``ndr_amd.modal.eigenmodes``, on assembled matrices with SuperLU's K^-1 as the preconditioner.
+
+Conventions: those of stress_cpu (last axis fastest, local node index with axis 0 as the most significant bit, dof = N node + c).
+
+    M0 = kron over the axes of h_d / 6 [[2, 1], [1, 2]], identity across components;  M = sum_e m_e M0,  m = massDensity rho^r
+    K phi = lambda M phi on the free dofs, phi^T M phi = 1
+    J = sum_{i <= k} 1 / lambda_i,   dJ/drho_e = -sum_i lambda_i^-2 (dE_e phi_ie^T K0 phi_ie - lambda_i dm_e phi_ie^T M0 phi_ie)
+"""
+import functools
+
+import numpy as np
+import scipy.linalg
+import scipy.sparse as sp
+import scipy.sparse.linalg as spla
+
+import homogenization_cpu as hc
+import stress_cpu as sc
+
+E0, EMIN, GAMMA = 1.0, 1e-3, 3.0
+NUM_MODES = 4
+# elements, edge lengths, (E, nu): the shapes of the stress tests; densities uniform in [0.2, 1] from default_rng(0), left face clamped
+CASES = {"16x12": ((16, 12), (0.125, 0.125), (1.0, 0.3)), "8x8x6": ((8, 8, 6), (0.25, 0.25, 0.25), (1.0, 0.3))}
+
+
+def mass_element(h):
+    """M0 [ke, ke] of a unit-density voxel with edge lengths h"""
+    N = len(h)
+    nodes = np.ones((1, 1))
+    for d in range(N):
+        nodes = np.kron(nodes, h[d] / 6.0 * np.array([[2.0, 1.0], [1.0, 2.0]]))
+    return np.kron(nodes, np.eye(N))
+
+
+def mass_multipliers(rho, massDensity=1.0, massExponent=1.0, lowDensityCut=None):
+    """(m, dm/drho); below the cut Du & Olhoff's massDensity (6 rho^6 / c^5 - 5 rho^7 / c^6)"""
+    rho = np.asarray(rho, dtype=np.float64).reshape(-1)
+    m, dm = massDensity * rho ** massExponent, massDensity * massExponent * rho ** (massExponent - 1.0)
+    if lowDensityCut is not None:
+        c = float(lowDensityCut)
+        low = rho < c
+        m = np.where(low, massDensity * (6.0 * rho ** 6 / c ** 5 - 5.0 * rho ** 7 / c ** 6), m)
+        dm = np.where(low, massDensity * (36.0 * rho ** 5 / c ** 5 - 35.0 * rho ** 6 / c ** 6), dm)
+    return m, dm
+
+
+def assemble_mass(ne, h, m, fixed=None):
+    """M (csr) on the full node grid; with ``fixed`` the rows and columns of the fixed dofs are zero (P M P)"""
+    dofs = sc.element_dofs(ne)
+    ke = dofs.shape[1]
+    nd = sc.num_nodes(ne) * len(ne)
+    rows, cols = np.repeat(dofs, ke, axis=1).reshape(-1), np.tile(dofs, (1, ke)).reshape(-1)
+    M = sp.coo_matrix(((np.asarray(m)[:, None, None] * mass_element(h)[None]).reshape(-1), (rows, cols)), shape=(nd, nd)).tocsr()
+    if fixed is not None:
+        P = sp.diags(1.0 - np.asarray(fixed, dtype=np.float64).reshape(-1))
+        M = (P @ M @ P).tocsr()
+    return M
+
+
+def case(name):
+    """(ne, h, D, rho, fixed [numNodes, N])"""
+    ne, h, (E, nu) = CASES[name]
+    rho = np.random.default_rng(0).uniform(0.2, 1.0, size=int(np.prod(ne)))
+    return ne, h, hc.isotropic_D(E, nu, len(ne)), rho, sc.cantilever(ne)[0]
+
+
+def operators(ne, h, D, rho, fixed, mass=None):
+    """dict with K0, M0, dE, dm, the free dofs, and K, M (csr) reduced to them"""
+    K0 = hc.element_constants(D, h)[0]
+    E, dE = hc.moduli(rho, E0, EMIN, GAMMA)
+    m, dm = mass_multipliers(rho, **(mass or {}))
+    free = np.flatnonzero(~np.asarray(fixed, dtype=bool).reshape(-1))
+    K = sc.assemble(ne, K0, E, fixed)[free][:, free].tocsr()
+    M = assemble_mass(ne, h, m)[free][:, free].tocsr()
+    return dict(ne=ne, K0=K0, M0=mass_element(h), dE=dE, dm=dm, m=m, free=free, K=K, M=M, ndof=sc.num_nodes(ne) * len(ne))
+
+
+def dense_modes(op, k):
+    """(lambda [k], Phi [ndof, k] on the full grid, M-orthonormal) by the dense generalised eigensolver"""
+    lam, V = scipy.linalg.eigh(op["K"].toarray(), op["M"].toarray())
+    Phi = np.zeros((op["ndof"], k))
+    Phi[op["free"]] = V[:, :k]
+    return lam[:k], Phi, lam
+
+
+def objective(lam):
+    return float(np.sum(1.0 / lam))
+
+
+def gradient(op, lam, Phi):
+    dofs = sc.element_dofs(op["ne"])
+    g = np.zeros(len(dofs))
+    for i in range(len(lam)):
+        pe = Phi[:, i][dofs]
+        g -= lam[i] ** -2.0 * (op["dE"] * np.einsum("ek,kl,el->e", pe, op["K0"], pe)
+                               - lam[i] * op["dm"] * np.einsum("ek,kl,el->e", pe, op["M0"], pe))
+    return g
+
+
+# ---- LOBPCG with the basis handling of ndr_amd.modal ----
+
+RANK_TOL = 1e-3         # see ndr_amd.modal._RANK_TOL; 1e-7 let the residuals jump back from 1e-11 to 1e-8, 1e-2 stalled 8 x 8 x 6 at 5e-7
+
+def orthonormalising_map(GM, keep):
+    G = GM[np.ix_(keep, keep)]
+    d = np.diag(G).copy()
+    live = d > 0.0
+    if not live.any() or not np.isfinite(G).all():
+        return None
+    idx = np.flatnonzero(live)
+    s = 1.0 / np.sqrt(d[idx])
+    try:
+        L = np.linalg.cholesky(G[np.ix_(idx, idx)] * s[:, None] * s[None, :])
+    except np.linalg.LinAlgError:
+        return None
+    if not np.isfinite(L).all() or np.diag(L).min() < RANK_TOL:
+        return None
+    B = np.zeros((GM.shape[0], len(idx)))
+    B[np.asarray(keep)[idx]] = s[:, None] * np.linalg.solve(L, np.eye(len(idx))).T
+    return B
+
+
+def rayleigh_ritz(GK, GM, m):
+    """basis [X, W, P]: (theta [m], CX, CP, dropped)"""
+    GK, GM = 0.5 * (GK + GK.T), 0.5 * (GM + GM.T)
+    dropped = False
+    B = orthonormalising_map(GM, list(range(3 * m)))
+    if B is None:
+        dropped = True
+        B = orthonormalising_map(GM, list(range(2 * m)))
+    if B is None:
+        B = orthonormalising_map(GM, list(range(m)))
+    if B is None:
+        raise RuntimeError("the block has lost its rank")
+    A = B.T @ GK @ B
+    theta, Y = np.linalg.eigh(0.5 * (A + A.T))
+    CX = B @ Y[:, :m]
+    CP = CX.copy()
+    CP[:m] = 0.0
+    return theta[:m], CX, CP, dropped
+
+
+def lobpcg(K, M, k, tol, X0, guard=2, max_iter=200, T=None):
+    """(lambda [k], X [n, k], iterations, residuals): the k lowest eigenpairs of K x = lambda M x; ``T`` applies the preconditioner to
+    a block (default: SuperLU's K^-1); residuals |K x - lambda M x| / (lambda |M x|); iterations = Rayleigh-Ritz updates"""
+    n = K.shape[0]
+    m = min(k + guard, n)
+    if T is None:
+        lu = spla.splu(K.tocsc())
+        T = lu.solve
+    X = np.array(X0[:, :m], dtype=np.float64)
+    G3, H3 = np.zeros((3 * m, 3 * m)), np.zeros((3 * m, 3 * m))
+    G3[:m, :m], H3[:m, :m] = X.T @ (K @ X), X.T @ (M @ X)
+    lam, CX, _, _ = rayleigh_ritz(G3, H3, m)
+    X = X @ CX[:m]
+    P = np.zeros_like(X)
+    for it in range(max_iter + 1):
+        KX, MX = K @ X, M @ X
+        R = KX - MX * lam
+        res = np.linalg.norm(R, axis=0) / (np.abs(lam) * np.linalg.norm(MX, axis=0))
+        if res[:k].max() <= tol:
+            return lam[:k], X[:, :k], it, res[:k]
+        if it == max_iter:
+            break
+        S = np.hstack([X, T(R), P])
+        lam, CX, CP, _ = rayleigh_ritz(S.T @ (K @ S), S.T @ (M @ S), m)
+        X, P = S @ CX, S @ CP
+    raise RuntimeError("lobpcg: no convergence in %d iterations: the worst residual is %.3e" % (max_iter, res[:k].max()))
+
+
+def start_block(op, columns, seed=7):
+    return np.random.default_rng(seed).standard_normal((len(op["free"]), columns))
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name, k=NUM_MODES):
+    """the dense solution of a case, computed once and shared (tests leave it unchanged)"""
+    ne, h, D, rho, fixed = case(name)
+    op = operators(ne, h, D, rho, fixed)
+    lam, Phi, spectrum = dense_modes(op, k)
+    return dict(op=op, lam=lam, Phi=Phi, spectrum=spectrum, J=objective(lam), gradient=gradient(op, lam, Phi))
