@@ -52,7 +52,7 @@ enum {
     VFEM_OPT_GS_VARIANT   = 2,   /* 0 production sweeps, 1 plain gather sweeps */
     VFEM_OPT_APPLY_IMPL   = 4,   /* 0 LDS-DMA apply, 1 register-staged apply */
     VFEM_OPT_Q2_IMPL      = 6,   /* vfem_gsim: degree-2 apply 0 marching, 1 dense gather, 2 pencil */
-    VFEM_OPT_DMA_CHUNKS   = 7,   /* x-chunks of the marching apply (0 = default) */
+    VFEM_OPT_DMA_CHUNKS   = 7,   /* x-chunks of the marching apply (0 = default: the balanced one-block-per-CU schedule; n > 0: one block per tile and chunk, 8 = its default tiling) */
     VFEM_OPT_DMA_STRIP    = 9,   /* z-remainder strip tiles: 0 off, 1 on, 2 on with the main chunk length */
     VFEM_OPT_DMA_LX       = 11,  /* z tiling of the LDS-DMA apply whose tile boundaries fall on 128-byte lines of the result (tiles advance by 57 columns):
                                     0 off (default: measured 8 % slower at 512^3 -- nine full tiles against eight and a strip --, profiles/r04_apply_lx.txt),

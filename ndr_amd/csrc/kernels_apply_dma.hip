@@ -77,11 +77,19 @@ struct DmArgs2 { double v[36]; };
 
 // RES: out = b - K u with 0 at the fixed components (the residual of the V-cycle) instead of K u: right-hand side and mask of the
 // node a thread emits are requested one phase ahead, before the arithmetic of the plane in between
-template <int EXP, class C, bool RES = false, bool LX = false>
+//
+// One call marches the tile (ztile, ytile) of shape C over the output planes [p0, p1]; carry and fold start from the plane below p0,
+// so where a march is cut in x changes no sum.  A block may call it several times in a row (k_apply_dma_sched): inside one call the
+// DMA waves and the compute waves execute the same number of barriers -- 2 for the prologue, one per plane i_start + 1 .. i_end, one
+// more when p1 is the last plane of the grid -- so all 14 waves leave a call in step, and the caller puts one closing barrier
+// behind it before the DMA waves request the next call's planes into the ring and the scatter buffers are written again.
+// REPEAT (the caller's loop over calls): lane and wave pass through an empty asm, so that nothing derived from them is hoisted out of
+// that loop -- hipcc otherwise computes the lane-only parts of both tile shapes' offsets ahead of it and keeps them in scratch.
+template <int EXP, class C, bool RES = false, bool LX = false, bool REPEAT = false>
 __device__ __forceinline__ void apply_tile(const Dims &d, const DmArgs2 &dm, const double *__restrict__ E,
                                            const double *__restrict__ u, double *__restrict__ out,
-                                           int planes_per_chunk, const char *u_last, const char *e_last,
-                                           int plane_lo, int plane_hi, int kz_origin, int ztile, int ytile, int adv, int hi_node,
+                                           const char *u_last, const char *e_last,
+                                           int p0, int p1, int kz_origin, int ztile, int ytile, int adv, int hi_node,
                                            const double *__restrict__ rhs = nullptr, const uint8_t *__restrict__ fixed = nullptr) {
     using namespace dma;
     constexpr int TY = C::TY, TZ = C::TZ, PU = C::PU, PE = C::PE, ROW_D = C::ROW_D, EROW_D = C::EROW_D;
@@ -95,7 +103,8 @@ __device__ __forceinline__ void apply_tile(const Dims &d, const DmArgs2 &dm, con
     unsigned char *ring = smem;
     double *sS = reinterpret_cast<double *>(smem + (size_t) RING * SLOT_BYTES);
 
-    const int lane = threadIdx.x, wave = threadIdx.y;
+    int lane = threadIdx.x, wave = threadIdx.y;
+    if (REPEAT) asm volatile("" : "+v"(lane), "+v"(wave));
     const int tz = lane % TZ, ty = wave * C::SUB + lane / TZ;     // element column / row inside the tile (compute waves)
     // The tile computes complete sums for the node columns k0 + 1 .. k0 + TZ - 1 and EMITS those in [k0 + 1, hi_node) -- the next tile's
     // first column, `adv` columns on (TZ - 1 = 63 in the plain tiling).  Line-exclusive tiling (lx, round 4; VERDICT r03 item 5,
@@ -105,10 +114,6 @@ __device__ __forceinline__ void apply_tile(const Dims &d, const DmArgs2 &dm, con
     // one node per row and per plane.  (A 64-lane wave has 63 complete columns: 57 + the 6 a line can reach back over.)
     const int k0 = kz_origin + ztile * adv - 1;
     const int j0 = ytile * (TY - 1) - 1;
-    const int p0 = plane_lo + blockIdx.x * planes_per_chunk;      // output planes [p0, p1] of [plane_lo, plane_hi]
-    int p1 = p0 + planes_per_chunk - 1;
-    if (p1 > plane_hi) p1 = plane_hi;
-    if (p0 > plane_hi) return;
     const int k0u = k0 < 0 ? 0 : k0;                   // first node column held by a staged row image
     const int cshift = k0u - k0;                       // 0, or 1 in the first z tile
 
@@ -442,11 +447,17 @@ __global__ void __launch_bounds__(64 * (dma::WAVES + dma::NW)) k_apply_dma(Dims 
     if ((int) blockIdx.y < n_main) {
         if ((int) blockIdx.z * (dma::Main::TY - 1) > d.NY - 1) return;      // the grid's z extent covers the main shape's y tiles
         const int hi = (int) blockIdx.y + 1 < n_main ? ((int) blockIdx.y + 1) * adv : strip_origin;
-        apply_tile<EXP, dma::Main, false, LX>(d, dm, E, u, out, planes_per_chunk, u_last, e_last, plane_lo, plane_hi, 0, (int) blockIdx.y, (int) blockIdx.z, adv, hi);
+        const int p0 = plane_lo + (int) blockIdx.x * planes_per_chunk;      // output planes [p0, p1] of [plane_lo, plane_hi]
+        if (p0 > plane_hi) return;
+        const int p1 = p0 + planes_per_chunk - 1 < plane_hi ? p0 + planes_per_chunk - 1 : plane_hi;
+        apply_tile<EXP, dma::Main, false, LX>(d, dm, E, u, out, u_last, e_last, p0, p1, 0, (int) blockIdx.y, (int) blockIdx.z, adv, hi);
     } else {
         if (EXP != 0 || (int) blockIdx.z >= strip_ytiles) return;
-        // the strip may use longer x-chunks than the main tiles (fewer, longer blocks); chunks beyond its last plane leave inside
-        if (EXP == 0) apply_tile<0, dma::Strip, false, LX>(d, dm, E, u, out, strip_ppc, u_last, e_last, plane_lo, plane_hi, strip_origin, 0, (int) blockIdx.z, dma::Strip::TZ - 1, d.NZ);
+        // the strip may use longer x-chunks than the main tiles (fewer, longer blocks); chunks beyond its last plane leave here
+        const int p0 = plane_lo + (int) blockIdx.x * strip_ppc;
+        if (p0 > plane_hi) return;
+        const int p1 = p0 + strip_ppc - 1 < plane_hi ? p0 + strip_ppc - 1 : plane_hi;
+        if (EXP == 0) apply_tile<0, dma::Strip, false, LX>(d, dm, E, u, out, u_last, e_last, p0, p1, strip_origin, 0, (int) blockIdx.z, dma::Strip::TZ - 1, d.NZ);
     }
 }
 
@@ -459,10 +470,73 @@ __global__ void __launch_bounds__(64 * (dma::WAVES + dma::NW)) k_residual_dma(Di
     if ((int) blockIdx.y < n_main) {
         if ((int) blockIdx.z * (dma::Main::TY - 1) > d.NY - 1) return;
         const int hi = (int) blockIdx.y + 1 < n_main ? ((int) blockIdx.y + 1) * adv : strip_origin;
-        apply_tile<0, dma::Main, true, LX>(d, dm, E, u, out, planes_per_chunk, u_last, e_last, plane_lo, plane_hi, 0, (int) blockIdx.y, (int) blockIdx.z, adv, hi, rhs, fixed);
+        const int p0 = plane_lo + (int) blockIdx.x * planes_per_chunk;
+        if (p0 > plane_hi) return;
+        const int p1 = p0 + planes_per_chunk - 1 < plane_hi ? p0 + planes_per_chunk - 1 : plane_hi;
+        apply_tile<0, dma::Main, true, LX>(d, dm, E, u, out, u_last, e_last, p0, p1, 0, (int) blockIdx.y, (int) blockIdx.z, adv, hi, rhs, fixed);
     } else {
         if ((int) blockIdx.z >= strip_ytiles) return;
-        apply_tile<0, dma::Strip, true, LX>(d, dm, E, u, out, strip_ppc, u_last, e_last, plane_lo, plane_hi, strip_origin, 0, (int) blockIdx.z, dma::Strip::TZ - 1, d.NZ, rhs, fixed);
+        const int p0 = plane_lo + (int) blockIdx.x * strip_ppc;
+        if (p0 > plane_hi) return;
+        const int p1 = p0 + strip_ppc - 1 < plane_hi ? p0 + strip_ppc - 1 : plane_hi;
+        apply_tile<0, dma::Strip, true, LX>(d, dm, E, u, out, u_last, e_last, p0, p1, strip_origin, 0, (int) blockIdx.z, dma::Strip::TZ - 1, d.NZ, rhs, fixed);
+    }
+}
+
+// The balanced schedule: one block per CU, each marching a list of segments (tile column x plane range) it derives from its own id.
+//   * Block b is slot b / 8 of team b % 8 -- the XCD it runs on, block ids being dealt round-robin to the 8 XCDs; a different
+//     dealing costs balance, never correctness: every segment belongs to exactly one block whatever the hardware does with it.
+//   * The planes [plane_lo, plane_hi] are cut into nslab slabs (8, 4 or 1) whose lengths differ by at most one; team t works on slab
+//     t % nslab, so the eight XCDs write eight distant slabs at once (the block order profiles/r03_apply_mixprobe.txt found best).
+//     The 8 / nslab teams of one slab split its tile columns into contiguous parts.
+//   * A team's columns are the main tiles (z tile fastest, then y tile) followed by the strip tiles.  In round r slot s marches
+//     column r S + s over the whole slab: neighbouring slots are z and y neighbours at the same plane at the same time, and their
+//     halo rows meet in the XCD's L2.  The C mod S columns left after the last whole round are L (C mod S) plane-steps, column by
+//     column; every slot takes q = ceil(L (C mod S) / S) of them in a row -- one piece of a column, or the end of one column and
+//     the beginning of the next -- plus the halo planes of each piece.
+// Everything is wave-uniform integer arithmetic on the block id: no table, no atomics, and every wave of a block sees the same list.
+struct DmaSched { int nslab, slots, n_main, ytiles, strip_ytiles, strip_origin, adv; };
+
+template <bool RES>
+__global__ void __launch_bounds__(64 * (dma::WAVES + dma::NW)) k_apply_dma_sched(Dims d, DmArgs2 dm, const double *__restrict__ E,
+                                                      const double *__restrict__ u, double *__restrict__ out,
+                                                      const char *u_last, const char *e_last, int plane_lo, int plane_hi, DmaSched sc,
+                                                      const double *__restrict__ rhs, const uint8_t *__restrict__ fixed) {
+    const int team = (int) blockIdx.x & 7, slot = (int) blockIdx.x >> 3, S = sc.slots;
+    const int slab = team % sc.nslab, part = team / sc.nslab, nparts = 8 / sc.nslab;
+    const long long np = plane_hi - plane_lo + 1;
+    const int a = plane_lo + (int) (slab * np / sc.nslab), b = plane_lo + (int) ((slab + 1) * np / sc.nslab) - 1;      // the slab
+    const int L = b - a + 1;
+    const int main_cols = sc.n_main * sc.ytiles, cols = main_cols + sc.strip_ytiles;
+    const int c_lo = (int) ((long long) part * cols / nparts), C = (int) ((long long) (part + 1) * cols / nparts) - c_lo;   // the team's columns
+    const int full = C / S, R = C - full * S;
+    // the remainder: plane-steps [w0, w1) of the R L that the columns c_lo + full S + (0 .. R - 1) hold, L to a column
+    const long long W = (long long) R * L, q = (W + S - 1) / S;
+    const long long w0 = slot * q < W ? slot * q : W, w1 = w0 + q < W ? w0 + q : W;
+    const int j0 = (int) (w0 / L), j1 = w1 > w0 ? (int) ((w1 - 1) / L) : j0;      // q <= L: a piece touches at most two columns
+    for (int seg = 0; seg < full + 2; ++seg) {
+        int col, p0 = a, p1 = b;
+        if (seg < full) col = seg * S + slot;
+        else if (seg == full) {
+            if (w1 <= w0) break;
+            col = full * S + j0;
+            p0 = a + (int) (w0 - (long long) j0 * L);
+            if (j1 == j0) p1 = a + (int) (w1 - 1 - (long long) j0 * L);
+        } else {
+            if (j1 == j0) break;
+            col = full * S + j1;
+            p1 = a + (int) (w1 - 1 - (long long) j1 * L);
+        }
+        col += c_lo;
+        if (col < main_cols) {
+            const int yt = col / sc.n_main, zt = col - yt * sc.n_main;
+            const int hi = zt + 1 < sc.n_main ? (zt + 1) * sc.adv : sc.strip_origin;
+            apply_tile<0, dma::Main, RES, false, true>(d, dm, E, u, out, u_last, e_last, p0, p1, 0, zt, yt, sc.adv, hi, rhs, fixed);
+        } else
+            apply_tile<0, dma::Strip, RES, false, true>(d, dm, E, u, out, u_last, e_last, p0, p1, sc.strip_origin, 0, col - main_cols, dma::Strip::TZ - 1, d.NZ, rhs, fixed);
+        // closing barrier of the segment (see apply_tile): all 14 waves have read what they need of the ring and the scatter buffers
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
     }
 }
 
@@ -509,7 +583,34 @@ bool launch_apply_dma(const Dims &d, const double *Dm_host, const double *E, con
     const int strip_ppc = (g_dma_strip == 2 || gx < 2) ? ppc : 2 * ppc;
     static_assert(Main::LDS_BYTES == Strip::LDS_BYTES, "both tile shapes use the same dynamic LDS size");
     const char *ul = last_piece(u_end), *el = last_piece(e_end);
-#define VFEM_DMA_LAUNCH2(X, L)                                                                                               \
+    // The default settings take the balanced schedule (k_apply_dma_sched); any other value of the three options -- dma_chunks = 8 is
+    // the same tiling in the launch below -- and the ablation variants take the grid launch of one block per tile and x-chunk.
+    if (g_dma_chunks == 0 && g_dma_strip == 1 && g_dma_lx == 0 && g_apply_skeleton == 0) {
+        static int cus[64];                     // per device, queried once
+        int dev = 0;
+        VFEM_HIP(hipGetDevice(&dev));
+        int ncu = 0;
+        if (dev >= 0 && dev < 64) ncu = cus[dev];
+        if (ncu == 0) {
+            VFEM_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
+            if (dev >= 0 && dev < 64) cus[dev] = ncu;
+        }
+        if (ncu >= 8) {
+            const DmaSched sc = {nchunks < 8 ? nchunks : 8, ncu / 8, n_main, ytiles, strip_ytiles, rem > 0 ? wz * n_main : d.NZ, wz};
+            const dim3 sgrd((unsigned) (8 * sc.slots), 1, 1);
+            static bool attr = false;
+            if (!attr) {
+                VFEM_HIP(hipFuncSetAttribute((const void *) k_apply_dma_sched<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) Main::LDS_BYTES));
+                VFEM_HIP(hipFuncSetAttribute((const void *) k_apply_dma_sched<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) Main::LDS_BYTES));
+                attr = true;
+            }
+            if (rhs) k_apply_dma_sched<true><<<sgrd, blk, Main::LDS_BYTES, s>>>(d, dm, E, u, out, ul, el, plane_lo, plane_hi, sc, rhs, fixed);
+            else k_apply_dma_sched<false><<<sgrd, blk, Main::LDS_BYTES, s>>>(d, dm, E, u, out, ul, el, plane_lo, plane_hi, sc, nullptr, nullptr);
+            VFEM_HIP(hipGetLastError());
+            return true;
+        }
+    }
+#define VFEM_DMA_LAUNCH2(X, L)                                                                                              \
     do {                                                                                                                     \
         static bool attr = false;                                                                                            \
         if (!attr) {                                                                                                         \

@@ -79,7 +79,7 @@ void launch_apply_stencil(const Dims &d, const double *S, const double *u, const
 struct Tuning {
     int apply_impl = 0;     // 0: LDS-DMA kernel (register-staged kernel when it cannot run), 1: register-staged kernel
     int apply_pd = 2;       // register-staged kernel: node planes in flight (2..4)
-    int dma_chunks = 0;     // x-chunks of the marching blocks (0 = default)
+    int dma_chunks = 0;     // x-chunks of the marching blocks (0 = default: the balanced schedule, launch_apply_dma)
     int dma_strip = 1;      // 0: main tile shape only, 1: strip tiles for the left-over node columns, 2: strip with main-length chunks
     int dma_lx = 0;         // line-exclusive z tiling of the LDS-DMA apply: 0 off (default: measured slower), 1 where it costs no extra z tile, 2 always
     int gs_variant = 0;     // 0: row-streaming / symmetric sweeps, 1: plain gather sweeps
