@@ -626,6 +626,33 @@ int vfem_modal_gradient(int dim, const int64_t *nelems_host, const double *h_hos
                         const double *cK_host, const double *cM_host, const double *dE, const double *dm, const double *Phi, double *g,
                         void *stream);
 
+/* ---- linearised buckling of a degree-1 grid: geometric stiffness, adjoint load, density gradient ----
+ * Handle-free, dim = 2 or 3.  Every entry point starts with nelems_host[dim], h_host[dim] and the flattened tensor D_host [S][S] as
+ * the element-stress section has them.  Blocks, the node mask and the alignment rule are those of the natural-frequency section;
+ * mG, dmG, dE, g (device) are [elements], u, v, a (device) are [node][dim].
+ * The consistent geometric stiffness of element e is the same scalar matrix on every component, linear in its displacements:
+ *   K_G,e[(n, a), (m, b)] = delta_ab mG[e] sum_j u_ej T_j[n][m],  T_j[n][m] = int_e grad N_n^T (C : B_j(x)) grad N_m dV,
+ * B_j the strain of a unit displacement at dof j; the 2^dim dim tables T_j are formed on the host from D_host and h_host by two
+ * Gauss points per axis (exact), uploaded once per (device, dim, h, D) and kept for the life of the process (at most 8 of them).
+ * vfem_buckling_geom_apply: Y_c = P K_G(mG, u) P X_c for the ncols (1 .. 24) columns; one thread per node forms its 3^dim couplings
+ *   once for all columns and components.  Y must not overlap X or u.
+ * vfem_buckling_adjoint_load: a = sum_i c_host[i] d(phi_i^T K_G(mG, u) phi_i)/du over the nmodes (1 .. 8) columns of Phi, zero where
+ *   the mask fixes a component: element e gives mG[e] phi_ie^T T_j phi_ie (summed over the dim components of the mode) at dof j.
+ * vfem_buckling_gradient: g[e] = dmG[e] sum_i cG_host[i] sum_j u_ej phi_ie^T T_j phi_ie
+ *   + dE[e] (sum_i cK_host[i] phi_ie^T K0 phi_ie - v_e^T K0 u_e); K0_host [ke][ke] as in vfem_stress_pnorm_gradient.
+ * No atomics, fixed summation order: results are bit-identical run to run.  vfem_buckling_geom_apply and
+ * vfem_buckling_adjoint_load are asynchronous (but for the first call with a new h or D, which uploads the tables);
+ * vfem_buckling_gradient uploads K0 and synchronises the stream, as vfem_modal_gradient does.
+ * Refused before any device call: NULL pointers (but mask), dim not 2 or 3, extents < 1, h <= 0, a column or mode count out of
+ * range, a non-finite tensor, K0 or coefficient, and an output that overlaps an input. */
+int vfem_buckling_geom_apply(int dim, const int64_t *nelems_host, const double *h_host, const double *D_host, const double *mG,
+                             const double *u, const uint8_t *mask, int ncols, const double *X, double *Y, void *stream);
+int vfem_buckling_adjoint_load(int dim, const int64_t *nelems_host, const double *h_host, const double *D_host, const double *mG,
+                               const uint8_t *mask, int nmodes, const double *c_host, const double *Phi, double *a, void *stream);
+int vfem_buckling_gradient(int dim, const int64_t *nelems_host, const double *h_host, const double *D_host, int nmodes,
+                           const double *K0_host, const double *cG_host, const double *cK_host, const double *dmG, const double *dE,
+                           const double *u, const double *v, const double *Phi, double *g, void *stream);
+
 /* ---- timers: BENCHMARK_* registry (MeshFEM GlobalBenchmark.hh / Timer.hh; VoxelFEM.cc:245-255) ---- */
 int vfem_timers_reset(void);
 int vfem_timers_report(char *buf_host, size_t buf_len);

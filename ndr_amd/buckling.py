@@ -1,0 +1,307 @@
+"""Linearised buckling of a solved design on the device: the consistent geometric stiffness K_G(rho, u), the lowest load factors of
+(K + lambda K_G) phi = 0  by the block eigensolver of ``ndr_amd.modal``, and a p-norm measure of them with its density gradient by one
+adjoint solve.
+
+    u = compliance._u                                        # or sim.solve_device(f): the displacement of the reference load
+    lambdas, Phi, info = bucklingModes(sim, u, 4)            # ascending positive load factors, Phi [4, numNodes, N] K-orthonormal
+    obj = BucklingObjective(compliance); J, dJ = obj.evaluate(), obj.gradient_device()
+    cap = mma.ObjectiveConstraint(obj, upperBound=1 / lambdaMin)    # "buckles at no less than lambdaMin times the load"
+    loss = bucklingMeasure(densities, obj)                   # the same as an autograd node
+
+for a degree-1 simulator in 2-D (plane stress) or 3-D holding any material, at least one Dirichlet component and zero Dirichlet
+values.  The numerics run in ``libvfem.so`` (``vfem_buckling_*``, ``vfem_modal_project``, ``vfem_block_*``, include/vfem.h); DESIGN
+3.14 has the formulas.
+
+    K_G,e[(n,a),(m,b)] = delta_ab int_e grad N_n^T sigma_e(x) grad N_m dV,  sigma_e(x) = mG(rho_e) C : sym grad u(x): the consistent
+        geometric stiffness, integrated exactly;  mG(rho) = rho^q E_0, q = ``stressExponent`` (None: q = gamma) with NO E_min term
+        (Ferrari & Sigmund): void carries no geometric stiffness, or the lowest modes are wrinkles of the void
+    K_G phi = nu K phi on the free components, phi^T K phi = 1;  the wanted modes have the lowest (most negative) nu,  lambda = -1 / nu
+    J = (sum_{i <= k} mu_i^P)^(1/P),  mu_i = 1 / lambda_i = -nu_i:  1 / J <= lambda_1, so  J <= bound  caps the critical load from below
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib, modal
+from .pyVoxelFEM import _dev, _ptr, _stream, _to_np
+from .stress import _Grid as _StressGrid
+
+__all__ = ["geometricMultipliers", "applyKG", "applyKG_device", "bucklingModes", "BucklingObjective", "BucklingFunction",
+           "bucklingMeasure", "MAX_MODES"]
+
+MAX_MODES = modal.MAX_MODES
+
+
+def _dp(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+class _Grid(_StressGrid):
+    """what every ``vfem_buckling_*`` call starts with (the grid, the edge lengths, the tensor: ``stress._Grid``, which refuses
+    degree 2 and slab padding), the node mask and the block helpers of ``modal._Grid``"""
+
+    def __init__(self, sim):
+        super().__init__(sim)
+        self.blocks = modal._Grid(sim)
+        self.n, self.mask, self.fixed = self.blocks.n, self.blocks.mask, self.blocks.fixed
+
+    def multipliers(self, stressExponent):
+        """(mG, dmG/drho) of the simulator's densities: mG = rho^q E_0"""
+        sim = self.sim
+        q = float(sim.gamma if stressExponent is None else stressExponent)
+        if not q > 0.0:
+            raise RuntimeError("stressExponent must be positive (got %r)" % (stressExponent,))
+        rho = sim.getDensities_device()[:self.nelem]
+        E0 = float(sim.E_0)
+        return (rho ** q * E0).contiguous(), (q * rho ** (q - 1.0) * E0).contiguous()
+
+    def geom_apply(self, mG, u, X, Y, masked=True):
+        _lib.check(_lib.load().vfem_buckling_geom_apply(*self.head(), _ptr(mG), _ptr(u), _ptr(self.mask) if masked else None,
+                                                        X.shape[0], _ptr(X), _ptr(Y), _stream()))
+
+
+def geometricMultipliers(sim, stressExponent=None):
+    """(mG, dmG/drho) of the simulator's densities on the device: mG = rho^q E_0, q = ``stressExponent`` (None: the simulator's gamma)"""
+    return _Grid(sim).multipliers(stressExponent)
+
+
+def applyKG_device(sim, u, X, stressExponent=None, project=True):
+    """Y = P K_G(rho, u) P X for a vector [numNodes, N] or a block [columns <= 24, numNodes, N]; ``project=False``: Y = K_G X, the
+    Dirichlet conditions ignored as ``applyK_device`` ignores them.  ``u`` [numNodes, N] is the displacement that stresses the design."""
+    g = _Grid(sim)
+    one = (X.dim() if isinstance(X, torch.Tensor) else np.ndim(X)) <= 2
+    Xb = g.blocks.block(X)
+    if Xb.shape[0] > 3 * modal.MAX_BLOCK:
+        raise RuntimeError("applyKG takes at most %d columns (got %d)" % (3 * modal.MAX_BLOCK, Xb.shape[0]))
+    Y = torch.empty_like(Xb)
+    g.geom_apply(g.multipliers(stressExponent)[0], g.displacement(u), Xb, Y, masked=project)
+    return Y[0] if one else Y
+
+
+def applyKG(sim, u, X, stressExponent=None, project=True):
+    return _to_np(applyKG_device(sim, u, X, stressExponent, project))
+
+
+def _check_modes(who, numModes):
+    k = int(numModes)
+    if k < 1 or k > MAX_MODES:
+        raise RuntimeError("%s: numModes must be 1 to %d (got %r)" % (who, MAX_MODES, numModes))
+    return k
+
+
+def _check_clamped(who, g):
+    sim = g.sim
+    if np.any(sim._dvals[sim._mask] != 0):
+        raise RuntimeError("%s: nonzero Dirichlet values are not supported (the modes are those of the clamped body)" % who)
+    if not g.fixed:
+        raise RuntimeError("%s: the simulator has no Dirichlet component: a free body has rigid modes, K is singular and neither the "
+                           "load case nor the preconditioner K^-1 is defined; clamp it somewhere" % who)
+
+
+def bucklingModes(sim, u, numModes, tol=1e-8, maxIter=200, preconditioner="auto", X0=None, numGuard=None, stressExponent=None,
+                  mgSmoothingIterations=2):
+    """The ``numModes`` (1 .. 8) lowest positive load factors of  (K(rho) + lambda K_G(rho, u)) phi = 0  on the free components.
+
+    Returns ``(loadFactors, Phi, info)``: ``loadFactors`` [numModes] numpy ascending and positive, ``Phi`` [numModes, numNodes, N] on
+    the device, K-orthonormal and zero at the Dirichlet components, ``info`` as ``modal.eigenmodes`` returns it (``iterations``,
+    ``residuals`` = |K_G phi - nu K phi| / (|nu| |K phi|), ``blockSize``, ``droppedP``, ``X``: the converged block, guard columns
+    included, to hand back as ``X0``) plus ``nu`` [numModes], the eigenvalues as solved for: lambda = -1 / nu.
+
+    The eigenproblem is solved as  K_G phi = nu K phi  for the lowest nu by the LOBPCG loop of ``modal.eigenmodes``: K_G, symmetric
+    and indefinite, stands where K stands there, K where the mass stands, and K^-1 is the preconditioner (``preconditioner``,
+    ``mgSmoothingIterations``, ``numGuard``, ``X0``, ``tol`` and ``maxIter`` mean what they mean there).  A converged block in which
+    one of the ``numModes`` lowest nu is not negative raises: the load puts too little of the design under compression.  (With
+    K^-1 as the preconditioner the negative end of the spectrum of K^-1 K_G is the fast one; the nu near zero are where that
+    spectrum accumulates.  On any but a tiny grid a load with fewer compressed modes than asked for therefore usually ends in the
+    "no convergence" error instead, which names a nu that is positive or close to zero: ask for fewer modes.)"""
+    g = _Grid(sim)
+    k = _check_modes("bucklingModes", numModes)
+    _check_clamped("bucklingModes", g)
+    guard = min(2, modal.MAX_BLOCK - k) if numGuard is None else int(numGuard)
+    if guard < 0 or k + guard > modal.MAX_BLOCK:
+        raise RuntimeError("bucklingModes: numModes + numGuard must be at most %d (got %d + %d)" % (modal.MAX_BLOCK, k, guard))
+    m = min(k + guard, int((~sim._mask).sum()))
+    if m < k:
+        raise RuntimeError("bucklingModes: %d modes asked for, the simulator has %d free components" % (k, m))
+    u = g.displacement(u)
+    if not bool(torch.isfinite(u).all()) or float(u.abs().max()) == 0.0:
+        raise RuntimeError("bucklingModes: the displacement is zero or not finite: an unloaded design has no buckling modes")
+    mG = g.multipliers(stressExponent)[0]
+    T = modal._Preconditioner(sim, preconditioner, mgSmoothingIterations)
+
+    def apply_kg(X, out):
+        g.geom_apply(mG, u, X, out)
+
+    def apply_k(X, out):
+        for j in range(X.shape[0]):
+            out[j].copy_(sim.applyK_device(X[j]))
+        g.blocks.project(out)
+
+    nu, Phi, info = modal._lobpcg(g.blocks, k, m, apply_kg, apply_k, T, float(tol), int(maxIter), X0, who="bucklingModes", value="nu",
+                                  hint="are the densities positive and the displacement finite?")
+    negative = int((nu < 0.0).sum())
+    if negative < k:
+        raise RuntimeError("bucklingModes: %d buckling modes asked for, %d found: %d of the %d lowest nu are not negative (nu = %s); "
+                           "the load puts too little of the design under compression to have that many" %
+                           (k, negative, k - negative, k, " ".join("%.3e" % v for v in nu)))
+    info["nu"] = nu
+    return -1.0 / nu, Phi, info
+
+
+class BucklingObjective:
+    """J(rho) = (sum_{i <= numModes} lambda_i^-P)^(1/P) of the load factors of the problem a compliance objective solves: a smooth
+    upper bound of 1 / lambda_1 (``1 / J <= lambda_1 <= numModes^(1/P) / J``), so minimising it, or capping it, raises the critical
+    load.  Symmetric in the modes, so it stays differentiable where load factors inside the block cross, which lambda_1 alone does
+    not.  ``P = 1`` is sum 1 / lambda_i, the measure of ``modal.MeanEigenvalueObjective``.
+
+    ``solved`` is a ``ComplianceObjective`` or a ``MultigridComplianceObjective``: this objective shares its simulator, load, solver
+    settings and displacement, exactly as ``stress.PNormStressObjective`` does.  ``updateCache(xPhys)`` updates ``solved`` (one primal
+    solve); the eigensolve follows at the first use, once per displacement (``solved._u`` is a new tensor with every solve), and is
+    warm-started from the last converged block, guard columns included.  ``gradient_device()`` adds one adjoint solve for all modes
+    together, through the path ``PNormStressObjective.adjoint_device`` takes.  With w_i = (mu_i / J)^(P-1), mu_i = 1 / lambda_i = -nu_i:
+
+        a = -sum_i w_i d(phi_i^T K_G(rho, u) phi_i)/du   (0 at the Dirichlet components),    K v = a,
+        dJ/drho_e = -sum_i w_i [dmG_e sum_j u_ej phi_ie^T T_j phi_ie - nu_i dE_e phi_ie^T K0 phi_ie] - dE_e v_e^T K0 u_e,
+        dE = gamma rho^(gamma-1) (E_0 - E_min),  dmG = q rho^(q-1) E_0,  K_G,e = mG_e sum_j u_ej T_j.
+
+    ``preconditioner`` "auto": ``sim.solve_device`` (the band factor ``solved`` has just used), or, for a multigrid objective, one
+    V-cycle of its hierarchy.  ``tol``, ``maxIter``, ``numGuard`` are those of ``bucklingModes``.
+
+    Not an objective for ``OCOptimizer``: the optimality-criterion step takes sqrt(-dJ/drho) and so needs a gradient that is nowhere
+    positive, which compliance has and this measure has not: material added where the load case is in tension stresses the
+    compressed members harder.  On a 16 x 12 cantilever with random densities 42 entries are positive and 150 negative
+    (tests/test_buckling_cpu.py).  Minimise it, or cap it, with ``ndr_amd.mma.MMAOptimizer``, which takes gradients of either sign
+    (the usual use, as a constraint: ``mma.ObjectiveConstraint(BucklingObjective(compliance), upperBound=1 / lambdaMin)``), or use
+    ``bucklingMeasure`` with a torch optimiser or the MLP density field."""
+
+    def __init__(self, solved, numModes=4, P=8.0, stressExponent=None, tol=1e-8, maxIter=200, preconditioner="auto", numGuard=None):
+        P = float(P)
+        if not np.isfinite(P) or P < 1.0:
+            raise RuntimeError("BucklingObjective: P must be finite and at least 1 (got %r)" % (P,))
+        if not (hasattr(solved, "_sim") and hasattr(solved, "_u") and hasattr(solved, "updateCache")):
+            raise TypeError("BucklingObjective takes a ComplianceObjective or a MultigridComplianceObjective")
+        _check_clamped("BucklingObjective", _Grid(solved._sim))        # (_Grid refuses what the kernels do not take)
+        if stressExponent is not None and not float(stressExponent) > 0.0:
+            raise RuntimeError("stressExponent must be positive (got %r)" % (stressExponent,))
+        self.numModes = _check_modes("BucklingObjective", numModes)
+        self._solved, self._sim = solved, solved._sim
+        self.P, self.stressExponent = P, stressExponent
+        self.tol, self.maxIter, self.preconditioner, self.numGuard = float(tol), int(maxIter), preconditioner, numGuard
+        self._state = self._block = None
+
+    @property
+    def solved(self):
+        return self._solved
+
+    def updateCache(self, xPhys):
+        self._state = None
+        self._solved.updateCache(xPhys)
+
+    def _need(self):
+        """the modes of the displacement ``solved`` holds now; computed once per displacement"""
+        u = self._solved._u
+        st = self._state
+        if st is None or st["u"] is not u:
+            s = self._solved
+            T = self.preconditioner
+            if isinstance(T, str) and T == "auto" and getattr(s, "_mg", None) is not None:
+                T = s._mg
+            smoothing = int(getattr(s, "mgSmoothingIterations", 2))
+            lam, Phi, info = bucklingModes(self._sim, u, self.numModes, self.tol, self.maxIter, T, X0=self._block,
+                                           numGuard=self.numGuard, stressExponent=self.stressExponent, mgSmoothingIterations=smoothing)
+            self._block = info["X"]
+            mu = -info["nu"]
+            top = float(mu.max())
+            J = top * float(np.sum((mu / top) ** self.P)) ** (1.0 / self.P)
+            st = self._state = dict(u=u, grid=_Grid(self._sim), lam=lam, nu=info["nu"], Phi=Phi.contiguous(), info=info, J=J,
+                                    w=(mu / J) ** (self.P - 1.0), a=None, v=None, grad=None)
+        return st
+
+    def evaluate(self, xPhys=None):
+        if xPhys is not None:
+            self.updateCache(xPhys)
+        return self._need()["J"]
+
+    def loadFactors(self):
+        return self._need()["lam"].copy()
+
+    def modes_device(self):
+        return self._need()["Phi"]
+
+    def info(self):
+        return {k: v for k, v in self._need()["info"].items() if k != "X"}
+
+    def adjointLoad_device(self):
+        """dJ/du at fixed densities and modes, [numNodes, N], zero at the Dirichlet components"""
+        st = self._need()
+        if st["a"] is None:
+            g = st["grid"]
+            mG = g.multipliers(self.stressExponent)[0]
+            a = torch.empty((g.nnode, g.N), dtype=torch.float64, device=_dev())
+            c = np.ascontiguousarray(-st["w"])
+            _lib.check(_lib.load().vfem_buckling_adjoint_load(*g.head(), _ptr(mG), _ptr(g.mask), self.numModes, _dp(c), _ptr(st["Phi"]),
+                                                              _ptr(a), _stream()))
+            st["a"] = a
+        return st["a"]
+
+    def adjoint_device(self):
+        """v = K^-1 dJ/du by the solver that produced u; the operator has not changed, so nothing is factorised or rebuilt"""
+        st = self._need()
+        if st["v"] is None:
+            a, s = self.adjointLoad_device(), self._solved
+            mg = getattr(s, "_mg", None)
+            if mg is None:
+                st["v"] = self._sim.solve_device(a)
+            else:
+                st["v"] = mg.preconditionedConjugateGradient_device(torch.zeros_like(a), a, int(s.cgIter), float(s.tol), None,
+                                                                    int(s.mgIterations), int(s.mgSmoothingIterations),
+                                                                    bool(s.fullMultigrid))
+        return st["v"]
+
+    def gradient_device(self):
+        st = self._need()
+        if st["grad"] is None:
+            g, sim = st["grid"], self._sim
+            v = self.adjoint_device()
+            rho = sim.getDensities_device()[:g.nelem]
+            gamma = float(sim.gamma)
+            dE = (gamma * rho ** (gamma - 1.0) * (float(sim.E_0) - float(sim.E_min))).contiguous()
+            dmG = g.multipliers(self.stressExponent)[1]
+            K0 = np.ascontiguousarray(sim.fullDensityElementStiffnessMatrix())
+            cG, cK = np.ascontiguousarray(-st["w"]), np.ascontiguousarray(st["w"] * st["nu"])
+            out = torch.empty(g.nelem, dtype=torch.float64, device=_dev())
+            _lib.check(_lib.load().vfem_buckling_gradient(*g.head(), self.numModes, _dp(K0), _dp(cG), _dp(cK), _ptr(dmG), _ptr(dE),
+                                                          _ptr(st["u"]), _ptr(v.contiguous()), _ptr(st["Phi"]), _ptr(out), _stream()))
+            st["grad"] = out
+        return st["grad"].clone()
+
+    def gradient(self):
+        return _to_np(self.gradient_device())
+
+
+class BucklingFunction(torch.autograd.Function):
+    """J of the predicted densities as an autograd node, the counterpart of ``modal.MeanEigenvalueFunction``: forward sets the
+    densities, solves the load case and the eigenproblem; backward is ``gradient_device()`` weighted by the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, densities, objective):
+        objective.updateCache(densities.detach().reshape(-1))
+        J = objective.evaluate()
+        ctx.objective, ctx.u, ctx.dtype, ctx.shape = objective, objective.solved._u, densities.dtype, densities.shape
+        return torch.tensor(J, dtype=torch.float64, device=densities.device)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        obj = ctx.objective
+        if obj.solved._u is not ctx.u:
+            raise RuntimeError("bucklingMeasure: the objective was updated between forward and backward")
+        g = float(grad_output.detach().cpu()) * obj.gradient_device()
+        return g.to(ctx.dtype).reshape(ctx.shape), None
+
+
+def bucklingMeasure(densities, objective):
+    """J of ``objective`` (a ``BucklingObjective``) at the element densities ``densities`` (a device tensor of numElements values,
+    float32 or float64) as a differentiable float64 scalar: backward is grad_output x ``objective.gradient_device()`` in the
+    densities' dtype and shape.  The simulator is left holding these densities."""
+    return BucklingFunction.apply(densities, objective)

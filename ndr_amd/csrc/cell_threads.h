@@ -1,4 +1,4 @@
-// One thread per cell of a degree-1 grid (kernels_stress.hip, kernels_modal.hip): a block is 64 lanes along the last (fastest) axis
+// One thread per cell of a degree-1 grid (kernels_stress.hip, kernels_modal.hip, kernels_buckling.hip): a block is 64 lanes along the last (fastest) axis
 // by 4 rows of the axis before it; in 3-D blockIdx.z walks axis 0.  A "cell" is an element (extra = 0) or a node (extra = 1) of a
 // grid with ext[d] elements per axis.  Nodes and elements are numbered with the last axis fastest; element e owns the 2^N nodes
 // (e_d + mu_d), its local node index has axis 0 as the most significant bit.
@@ -10,6 +10,23 @@ namespace vfem {
 // position (0 / 1) along axis d of local node a: axis 0 is the most significant bit
 template <int N>
 __device__ __forceinline__ constexpr int node_bit(int a, int d) { return (a >> (N - 1 - d)) & 1; }
+
+// The 3^N nodes a node is coupled to (the node kernels of kernels_modal.hip and kernels_buckling.hip) are numbered in base 3.
+// offset (-1 / 0 / 1) along axis d of neighbour k: axis 0 is the most significant base-3 digit
+template <int N>
+__device__ __forceinline__ constexpr int neighbour_offset(int k, int d) {
+    int v = k;
+    for (int i = N - 1; i > d; --i) v /= 3;
+    return v % 3 - 1;
+}
+
+// the neighbour that local node j of the element in which this node is local node el stands for
+template <int N>
+__device__ __forceinline__ constexpr int neighbour_of(int el, int j) {
+    int k = 0;
+    for (int d = 0; d < N; ++d) k = 3 * k + (node_bit<N>(j, d) - node_bit<N>(el, d) + 1);
+    return k;
+}
 
 // the thread's cell of a grid with `ext[d] + extra` cells per axis; false: outside
 template <int N>

@@ -34,22 +34,6 @@ struct ModalTraits {
     static constexpr int NB = N == 2 ? 9 : 27;          // nodes coupled to a node
 };
 
-// offset (-1 / 0 / 1) along axis d of neighbour k: axis 0 is the most significant base-3 digit
-template <int N>
-__device__ __forceinline__ constexpr int neighbour_offset(int k, int d) {
-    int v = k;
-    for (int i = N - 1; i > d; --i) v /= 3;
-    return v % 3 - 1;
-}
-
-// the neighbour that local node j of the element in which this node is local node el stands for
-template <int N>
-__device__ __forceinline__ constexpr int neighbour_of(int el, int j) {
-    int k = 0;
-    for (int d = 0; d < N; ++d) k = 3 * k + (node_bit<N>(j, d) - node_bit<N>(el, d) + 1);
-    return k;
-}
-
 template <int N>
 __global__ void __launch_bounds__(256) k_modal_mass_apply(ModalGrid g, const double *__restrict__ m, const uint8_t *__restrict__ mask,
                                                           int ncols, const double *__restrict__ X, double *__restrict__ Y) {

@@ -248,6 +248,21 @@ def eigenmodes(sim, numModes, tol=1e-8, maxIter=200, preconditioner="auto", X0=N
     tol, maxIter = float(tol), int(maxIter)
     T = _Preconditioner(sim, preconditioner, mgSmoothingIterations)
     mult = massMultipliers(sim, **_mass_args(mass))[0]
+
+    def apply_k(X, out):
+        for j in range(X.shape[0]):
+            out[j].copy_(sim.applyK_device(X[j]))
+        g.project(out)
+
+    return _lobpcg(g, k, m, apply_k, lambda X, out: g.mass_apply(mult, X, out), T, tol, maxIter, X0)
+
+
+def _lobpcg(g, k, m, apply_a, apply_b, T, tol, maxIter, X0, who="eigenmodes", value="lambda",
+            hint="are the densities and the mass positive?"):
+    """The ``k`` lowest eigenpairs of  A x = lambda B x  on the free components of the grid ``g`` by LOBPCG on a block of ``m >= k``
+    columns: ``(lambdas [k], X [k, numNodes, N], info)`` as ``eigenmodes`` documents them.  ``apply_a(X, out)`` and
+    ``apply_b(X, out)`` write P A P X and P B P X for a block of up to m columns (B positive definite on the free components, A
+    symmetric); ``T(r)`` applies the preconditioner to one column.  ``who``, ``value`` and ``hint`` word the errors."""
     dev, f64 = _dev(), torch.float64
 
     # S = [W, P, X];  KM = [K W, K P, K X, M X, M P, M W]: K X and M X lie side by side for the residual, and the new P and X
@@ -262,11 +277,6 @@ def eigenmodes(sim, numModes, tol=1e-8, maxIter=200, preconditioner="auto", X0=N
     order_s = np.r_[2 * m:3 * m, 0:m, m:2 * m]
     order_m = np.r_[0:m, 2 * m:3 * m, m:2 * m]
 
-    def apply_k(X, out):
-        for j in range(X.shape[0]):
-            out[j].copy_(sim.applyK_device(X[j]))
-        g.project(out)
-
     # the starting block: given columns, the rest from the generator; then one Rayleigh-Ritz step on X alone
     X = S[0][2 * m:]
     rng = np.random.default_rng(20240229)
@@ -276,8 +286,8 @@ def eigenmodes(sim, numModes, tol=1e-8, maxIter=200, preconditioner="auto", X0=N
         given = g.block(X0)[:m]
         X[:given.shape[0]].copy_(given)
     g.project(X)
-    apply_k(X, KM[0][2 * m:3 * m])
-    g.mass_apply(mult, X, KM[0][3 * m:4 * m])
+    apply_a(X, KM[0][2 * m:3 * m])
+    apply_b(X, KM[0][3 * m:4 * m])
     _gram(X, KM[0][2 * m:3 * m], Grr)
     _gram(X, KM[0][3 * m:4 * m], Gmm)
     host = G[:2 * m * m].cpu().numpy()
@@ -287,8 +297,8 @@ def eigenmodes(sim, numModes, tol=1e-8, maxIter=200, preconditioner="auto", X0=N
     lam, CX, _, _ = _rayleigh_ritz(GK3, GM3, m)
     C0 = CX[:m]
     _combine(S[0][2 * m:], C0, S[1][2 * m:])
-    apply_k(S[1][2 * m:], KM[1][2 * m:3 * m])
-    g.mass_apply(mult, S[1][2 * m:], KM[1][3 * m:4 * m])
+    apply_a(S[1][2 * m:], KM[1][2 * m:3 * m])
+    apply_b(S[1][2 * m:], KM[1][3 * m:4 * m])
     cur = 1
     S[0].zero_()
     KM[0].zero_()
@@ -304,15 +314,15 @@ def eigenmodes(sim, numModes, tol=1e-8, maxIter=200, preconditioner="auto", X0=N
         for j in range(m):
             W[j].copy_(T(R[j]))
         g.project(W)
-        apply_k(W, km[:m])
-        g.mass_apply(mult, W, km[5 * m:])
+        apply_a(W, km[:m])
+        apply_b(W, km[5 * m:])
         _gram(s, km[:3 * m], Gk)
         _gram(s, km[3 * m:], Gm)
         host = G.cpu().numpy()                                   # the iteration's one synchronisation
         rr, mm = host[:m * m].reshape(m, m).diagonal(), host[m * m:2 * m * m].reshape(m, m).diagonal()
         res = np.sqrt(rr) / (np.abs(lam) * np.sqrt(mm))
         if not np.isfinite(res).all():
-            raise RuntimeError("eigenmodes: the residuals are not finite at iteration %d (are the densities and the mass positive?)" % it)
+            raise RuntimeError("%s: the residuals are not finite at iteration %d (%s)" % (who, it, hint))
         if res[:k].max() <= tol:
             X = s[2 * m:].clone()                                # (a view would keep both sets of the basis alive)
             info = dict(iterations=it, residuals=res[:k].copy(), blockSize=m, droppedP=dropped, X=X)
@@ -332,12 +342,12 @@ def eigenmodes(sim, numModes, tol=1e-8, maxIter=200, preconditioner="auto", X0=N
         # at hand and not of a recurrence that drifts from it
         _combine(km[:3 * m], Cs[:, :m], KM[nxt][m:2 * m])
         _combine(km[3 * m:], Cm[:, m:], KM[nxt][4 * m:5 * m])
-        apply_k(S[nxt][2 * m:], KM[nxt][2 * m:3 * m])
-        g.mass_apply(mult, S[nxt][2 * m:], KM[nxt][3 * m:4 * m])
+        apply_a(S[nxt][2 * m:], KM[nxt][2 * m:3 * m])
+        apply_b(S[nxt][2 * m:], KM[nxt][3 * m:4 * m])
         cur = nxt
     worst = int(np.argmax(res[:k]))
-    raise RuntimeError("eigenmodes: no convergence in %d iterations: the worst residual is %.3e (mode %d, lambda %.6e), "
-                       "tolerance %.3e" % (maxIter, res[worst], worst, lam[worst], tol))
+    raise RuntimeError("%s: no convergence in %d iterations: the worst residual is %.3e (mode %d, %s %.6e), "
+                       "tolerance %.3e" % (who, maxIter, res[worst], worst, value, lam[worst], tol))
 
 
 class MeanEigenvalueObjective:
