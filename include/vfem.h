@@ -653,6 +653,30 @@ int vfem_buckling_gradient(int dim, const int64_t *nelems_host, const double *h_
                            const double *K0_host, const double *cG_host, const double *cK_host, const double *dmG, const double *dE,
                            const double *u, const double *v, const double *Phi, double *g, void *stream);
 
+/* ---- load cases of a degree-1 grid: design-dependent loads and the gradient of a sum of compliances ----
+ * Handle-free, dim = 2 or 3.  Both entry points start with nelems_host[dim] and h_host[dim] as the natural-frequency section has
+ * them; the node mask and the alignment rule are those of that section.  m, E, dE, dm, g (device) are [elements], f_in, f_out
+ * (device) are [node][dim], U (device) is the block [case][node][dim].  An element pattern has ke = dim 2^dim entries, dof = dim
+ * node + component in the local node order of K0:
+ *   Lb[(n, a)] = vol / 2^dim g[a]  (the body force of an acceleration g on a unit mass density),
+ *   Lt[(n, a)] = sum_q sigma*[a][q] s_nq vol / (2^(dim-1) h_q),  sigma* = C : eps*, s_nq = +-1  (int B^T sigma* of an eigenstrain).
+ * vfem_loads_assemble: f_out = P (f_in + sum_e m[e] Lb + sum_e E[e] Lt).  Lb_host with m, or Lt_host with E, may be NULL, not both
+ *   pairs; f_in and mask may be NULL (zero; P = I).  f_out may be f_in; it overlaps nothing else.  One thread per node gathers its
+ *   2^dim elements in ascending local-node order; the patterns travel in the kernel arguments.  Asynchronous.
+ * vfem_loads_gradient: g[e] = dE[e] sum_i cK_host[i] u_ie^T K0 u_ie + dm[e] sum_i cB_host[i] Lb_i . u_ie
+ *   + dE[e] sum_i cT_host[i] Lt_i . u_ie over the ncases (1 .. 8) columns of U; K0_host [ke][ke] as in vfem_stress_pnorm_gradient,
+ *   Lb_host and Lt_host [ncases][ke].  Lb_host, cB_host and dm are NULL together, and so are Lt_host and cT_host.  One thread per
+ *   element reads its multipliers once for all cases.  It uploads K0 and the patterns and synchronises the stream, as
+ *   vfem_modal_gradient does.  g overlaps no input.
+ * No atomics, fixed summation order: results are bit-identical run to run.
+ * Refused before any device call: NULL pointers where one is required, dim not 2 or 3, extents < 1, h <= 0, ncases out of range,
+ * non-finite patterns, K0 or coefficients, and the overlaps named above. */
+int vfem_loads_assemble(int dim, const int64_t *nelems_host, const double *h_host, const double *Lb_host, const double *Lt_host,
+                        const double *m, const double *E, const uint8_t *mask, const double *f_in, double *f_out, void *stream);
+int vfem_loads_gradient(int dim, const int64_t *nelems_host, const double *h_host, int ncases, const double *K0_host,
+                        const double *cK_host, const double *cB_host, const double *cT_host, const double *Lb_host,
+                        const double *Lt_host, const double *dE, const double *dm, const double *U, double *g, void *stream);
+
 /* ---- timers: BENCHMARK_* registry (MeshFEM GlobalBenchmark.hh / Timer.hh; VoxelFEM.cc:245-255) ---- */
 int vfem_timers_reset(void);
 int vfem_timers_report(char *buf_host, size_t buf_len);

@@ -223,6 +223,10 @@ SIGNATURES = {
     "vfem_buckling_adjoint_load": (c_int, _STRESS + [c_void_p, c_void_p, c_int, POINTER(c_double), c_void_p, c_void_p, c_void_p]),
     "vfem_buckling_gradient": (c_int, _STRESS + [c_int, POINTER(c_double), POINTER(c_double), POINTER(c_double), c_void_p, c_void_p,
                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vfem_loads_assemble": (c_int, _MODAL + [POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p]),
+    "vfem_loads_gradient": (c_int, _MODAL + [c_int, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double),
+                                             POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vfem_timers_reset": (c_int, []),
     "vfem_timers_report": (c_int, [c_char_p, c_size_t]),
 }

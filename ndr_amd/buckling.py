@@ -181,6 +181,9 @@ class BucklingObjective:
             raise RuntimeError("BucklingObjective: P must be finite and at least 1 (got %r)" % (P,))
         if not (hasattr(solved, "_sim") and hasattr(solved, "_u") and hasattr(solved, "updateCache")):
             raise TypeError("BucklingObjective takes a ComplianceObjective or a MultigridComplianceObjective")
+        if getattr(solved, "designDependentLoad", False):
+            raise RuntimeError("BucklingObjective: the load of this case depends on the design (self-weight or eigenstrain): the "
+                               "adjoint gradient lacks the lambda^T df/drho term")
         _check_clamped("BucklingObjective", _Grid(solved._sim))        # (_Grid refuses what the kernels do not take)
         if stressExponent is not None and not float(stressExponent) > 0.0:
             raise RuntimeError("stressExponent must be positive (got %r)" % (stressExponent,))

@@ -498,6 +498,30 @@ class _GenericMultigridSolver(_MultigridSolver):
 # TensorProductSimulator<p,..,p>
 # ----------------------------------------------------------------------------------------------
 
+def _matched_regions(sim, bcPath):
+    """the regions of a boundary-condition file with the nodes their boxes hold (inclusive test on node coordinates), in file
+    order: (kind, comps, value, the matched indices per axis, their count)"""
+    N = sim.N
+    size = sim._bbmax - sim._bbmin
+    spacing = size / (sim._nn - 1.0)
+    coords = [sim._bbmin[d] + np.arange(sim._nn[d]) * spacing[d] for d in range(N)]
+    for kind, comps, value, lo, hi, relative in _parse_regions(bcPath):
+        lo, hi = np.array(lo[:N]), np.array(hi[:N])
+        if relative:
+            lo, hi = sim._bbmin + lo * size, sim._bbmin + hi * size
+        sel = [np.flatnonzero((coords[d] >= lo[d]) & (coords[d] <= hi[d])) for d in range(N)]
+        yield kind, comps, value, sel, int(np.prod([s.size for s in sel]))
+
+
+def _write_force_region(loads, sel, value, count):
+    """a force region into the device tensor ``loads`` [nodes per axis.., N]: split evenly over the matched nodes"""
+    if count == 0:
+        raise RuntimeError("Force constraint region unmatched")
+    N = loads.shape[-1]
+    ix = tuple(torch.from_numpy(sel[d]).to(_dev()).reshape([-1 if k == d else 1 for k in range(N)]) for d in range(N))
+    loads[ix] = torch.tensor(value[:N], dtype=torch.float64, device=_dev()) / count
+
+
 class _Simulator:
     """TensorProductSimulator<p,..,p> (VoxelFEM.cc:48-92; TPS.hh:219-1419) over a simulator handle of ``libvfem``: N
     dimensions, degree P.  The two subclasses name the C entry points (``_SIM_PREFIX``), create the handle and hold what
@@ -736,25 +760,13 @@ class _Simulator:
         split evenly over the matched nodes; Dirichlet components merge, conflicting values throw.  Force regions are
         written on the device: a host copy of the loads of a 513^3 grid would be 3.2 GB."""
         N = self.N
-        size = self._bbmax - self._bbmin
-        spacing = size / (self._nn - 1.0)
-        coords = [self._bbmin[d] + np.arange(self._nn[d]) * spacing[d] for d in range(N)]
         shape = tuple(self._nn)
         mask3 = self._mask.reshape(shape + (N,))
         vals3 = self._dvals.reshape(shape + (N,))
         loads = self._loads.reshape(shape + (N,))
-        for kind, comps, value, lo, hi, relative in _parse_regions(bcPath):
-            lo, hi = np.array(lo[:N]), np.array(hi[:N])
-            if relative:
-                lo, hi = self._bbmin + lo * size, self._bbmin + hi * size
-            sel = [np.flatnonzero((coords[d] >= lo[d]) & (coords[d] <= hi[d])) for d in range(N)]
-            count = int(np.prod([s.size for s in sel]))
+        for kind, comps, value, sel, count in _matched_regions(self, bcPath):
             if kind == "force":
-                if count == 0:
-                    raise RuntimeError("Force constraint region unmatched")
-                ix = tuple(torch.from_numpy(sel[d]).to(_dev()).reshape([-1 if k == d else 1 for k in range(N)])
-                           for d in range(N))
-                loads[ix] = torch.tensor(value[:N], dtype=torch.float64, device=_dev()) / count
+                _write_force_region(loads, sel, value, count)
             else:
                 if count == 0:
                     raise RuntimeError("Dirichlet region unmatched")
