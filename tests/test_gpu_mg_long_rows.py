@@ -19,7 +19,8 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import BC_CANTILEVER, make_hip, make_oracle, record_deltas, relerr, seeded_density, write_cut_bc
+from helpers import (BC_CANTILEVER, l0_pair_segments, l1_pair_segments, level_nodes, make_hip, make_oracle, record_deltas, relerr,
+                     seeded_density, write_cut_bc)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,32 +32,7 @@ GS_PAIR, GS_RESIDENT, STENCIL_SPLIT, GS_MARCH, L1_STORED, L1_MERGED = 10, 13, 18
 WAVE_SWEEP_MAX_NODES = 40000           # ndr_amd/csrc/vfem_internal.h
 
 
-# ---- the launchers' arithmetic, restated -------------------------------------------------------------------------------------------
-def l0_pair_segments(NZ, forward):
-    """k_gs_rows_mf0_pair on a level-0 row of NZ nodes: (nA, nB) segments of 64 nodes of the colour relaxed first / second.  The first
-    colour of a pair is c_z = 0 in a forward sweep (then B(s) waits for A(s + 1): lag 1) and c_z = 1 in a backward one."""
-    c1 = 0 if forward else 1
-    c2 = 1 - c1
-    nA = ((NZ - 1 - c1) // 2 + 1 + 63) // 64
-    nB = 0 if NZ - 1 - c2 < 0 else ((NZ - 1 - c2) // 2 + 1 + 63) // 64
-    return nA, nB
-
-
-def l1_pair_segments(NZ, forward):
-    """launch_l1_merged_sweep's pair branch on a level-1 row of NZ nodes: (nseg, A nodes left over, B nodes left over).  The A colour
-    is f_z = 0 forward (ka = 1: node k = 0 is always left over) and f_z = 1 backward (ka = 0)."""
-    fz = 0 if forward else 1
-    cntz = (NZ - 1 - fz) // 2 + 1
-    ka = 1 if fz == 0 else 0
-    nseg = (cntz - ka) // 64
-    walked = 64 * nseg
-    cntb = (NZ - 1 - (1 - fz)) // 2 + 1
-    return nseg, cntz - walked, cntb - walked
-
-
-def level_nodes(ne, l):
-    return tuple(n // 2 ** l + 1 for n in ne)
-
+# the launchers' arithmetic, restated: helpers.l0_pair_segments, helpers.l1_pair_segments
 
 # (shape, claims): claims["l0"] = forward / backward (nA, nB) of level 0, claims["l1"] = forward / backward (nseg, A left, B left) of
 # level 1; each with two coarsening levels
