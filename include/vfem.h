@@ -677,6 +677,50 @@ int vfem_loads_gradient(int dim, const int64_t *nelems_host, const double *h_hos
                         const double *cK_host, const double *cB_host, const double *cT_host, const double *Lb_host,
                         const double *Lt_host, const double *dE, const double *dm, const double *U, double *g, void *stream);
 
+/* ---- steady heat conduction on a degree-1 grid: scalar operator, solvers, gradient, flux ----
+ * Handle-free, dim = 2 or 3.  Every entry point starts with nelems_host[dim]; the two that need the voxel's edge lengths take
+ * h_host[dim] next.  The unknown is one temperature per node, nodes and elements numbered as in the natural-frequency section.
+ * kappa, dkappa, q, g (device) are [elements]; b, x, diag, f_in, f_out, T (device) are [nodes]; X, Y, A, B (device) are blocks
+ * [column][node]; flux (device) is [elements][dim]; fixed (device) is 1 byte per node, not 0 = the temperature is fixed at zero,
+ * and may be NULL (no fixed node).  Device pointers need 8-byte alignment only.  Kc0_host [2^dim][2^dim] is the conductivity
+ * matrix of a full-density voxel, int grad N_a^T k grad N_b dV, in the local node order of K0 (axis 0 the most significant bit).
+ * The operator is  A(kappa) = P (sum_e kappa[e] Kc0) P + (I - P),  P zeroing the fixed nodes: their rows and columns are the identity.
+ * vfem_thermal_apply: Y_c = A X_c for the ncols (1 .. 8) columns; one thread per node forms its 3^dim couplings once for all
+ *   columns.  Y overlaps no input.  Asynchronous.
+ * vfem_thermal_diagonal: diag = the diagonal of A (1 at a fixed node).  Asynchronous.
+ * vfem_thermal_source: f_out = P (f_in + sum_e q[e] vol / 2^dim), vol the voxel's volume: a nodal source and a volumetric source per
+ *   element.  q or f_in may be NULL, not both; f_out may be f_in and overlaps nothing else.  Asynchronous.
+ * vfem_thermal_band_assemble: the lower band of A in the tile layout of vfem_band_spd_factor, with n = nodes and w = the sum of the
+ *   node strides (1 + (ne[1] + 1) in 2-D, 1 + (ne[2] + 1) + (ne[1] + 1)(ne[2] + 1) in 3-D); band holds nb (bt + 2) 4096 doubles and every
+ *   entry of its slots 0 .. bt is written.  vfem_band_spd_factor and vfem_band_spd_solve do the rest.  Asynchronous.
+ * vfem_thermal_pcg: conjugate gradients with the Jacobi preconditioner on A x = b from the x given, until |r| / |b| <= tol (the
+ *   recurrence residual).  The host reads the residual once before the first iteration and then every 8 iterations, so the count
+ *   it returns is 0, a multiple of 8 or max_iter (after a breakdown: the iteration of the breakdown); b = 0 gives x = 0 in 0 iterations.  iterations_out_host and relres_out_host are
+ *   written on success and on the two failures: max_iter reached ("not converged after ..."), and a p . Ap that is not positive
+ *   ("breakdown at iteration ...": a singular operator or non-finite data; x is then unspecified).  Both messages carry the
+ *   residual.  x overlaps no input.  Synchronises the stream.
+ * vfem_thermal_gradient: g[e] = dkappa[e] sum_i c_host[i] a_ie^T Kc0 b_ie over the ncols (1 .. 8) column pairs of A and B; B may be
+ *   A.  One thread per element.  g overlaps no input.  Asynchronous.
+ * vfem_thermal_flux: flux[e] = -kappa[e] k grad T at the centre of element e, k_host [dim][dim] the conductivity tensor.  Asynchronous.
+ * No atomics, fixed summation order: results are bit-identical run to run.
+ * Refused before any device call: NULL pointers where one is required, dim not 2 or 3, extents < 1, h <= 0, a non-finite Kc0, tensor
+ * or coefficient, a column count out of range, tol <= 0, max_iter < 1, and the overlaps named above. */
+int vfem_thermal_apply(int dim, const int64_t *nelems_host, const double *Kc0_host, const double *kappa, const uint8_t *fixed,
+                       int ncols, const double *X, double *Y, void *stream);
+int vfem_thermal_diagonal(int dim, const int64_t *nelems_host, const double *Kc0_host, const double *kappa, const uint8_t *fixed,
+                          double *diag, void *stream);
+int vfem_thermal_source(int dim, const int64_t *nelems_host, const double *h_host, const double *q, const uint8_t *fixed,
+                        const double *f_in, double *f_out, void *stream);
+int vfem_thermal_band_assemble(int dim, const int64_t *nelems_host, const double *Kc0_host, const double *kappa, const uint8_t *fixed,
+                               double *band, void *stream);
+int vfem_thermal_pcg(int dim, const int64_t *nelems_host, const double *Kc0_host, const double *kappa, const uint8_t *fixed,
+                     const double *b, double *x, double tol, int max_iter, int *iterations_out_host, double *relres_out_host,
+                     void *stream);
+int vfem_thermal_gradient(int dim, const int64_t *nelems_host, int ncols, const double *Kc0_host, const double *c_host,
+                          const double *dkappa, const double *A, const double *B, double *g, void *stream);
+int vfem_thermal_flux(int dim, const int64_t *nelems_host, const double *h_host, const double *k_host, const double *kappa,
+                      const double *T, double *flux, void *stream);
+
 /* ---- timers: BENCHMARK_* registry (MeshFEM GlobalBenchmark.hh / Timer.hh; VoxelFEM.cc:245-255) ---- */
 int vfem_timers_reset(void);
 int vfem_timers_report(char *buf_host, size_t buf_len);

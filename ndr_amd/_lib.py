@@ -35,6 +35,9 @@ _STRESS = [c_int, POINTER(c_int64), POINTER(c_double), POINTER(c_double)]
 # what every vfem_modal_* grid entry point starts with: dim, nelems, h (host)
 _MODAL = [c_int, POINTER(c_int64), POINTER(c_double)]
 
+# what every vfem_thermal_* entry point starts with: dim, nelems (host)
+_THERMAL = [c_int, POINTER(c_int64)]
+
 # name -> (restype, argtypes); kept in one table so tests can check it against include/vfem.h
 SIGNATURES = {
     "vfem_last_error": (c_char_p, []),
@@ -227,6 +230,15 @@ SIGNATURES = {
                                              c_void_p]),
     "vfem_loads_gradient": (c_int, _MODAL + [c_int, POINTER(c_double), POINTER(c_double), POINTER(c_double), POINTER(c_double),
                                              POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vfem_thermal_apply": (c_int, _THERMAL + [POINTER(c_double), c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "vfem_thermal_diagonal": (c_int, _THERMAL + [POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vfem_thermal_source": (c_int, _THERMAL + [POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vfem_thermal_band_assemble": (c_int, _THERMAL + [POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vfem_thermal_pcg": (c_int, _THERMAL + [POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int, POINTER(c_int),
+                                            POINTER(c_double), c_void_p]),
+    "vfem_thermal_gradient": (c_int, _THERMAL + [c_int, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p]),
+    "vfem_thermal_flux": (c_int, _THERMAL + [POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p]),
     "vfem_timers_reset": (c_int, []),
     "vfem_timers_report": (c_int, [c_char_p, c_size_t]),
 }
