@@ -38,6 +38,7 @@ typedef struct vfem_gsim vfem_gsim;   /* TensorProductSimulator<p,..,p>, N = 2 o
                                          unbound in the reference (VoxelFEM.cc:226-229) */
 typedef struct vfem_hom_mg vfem_hom_mg; /* the multigrid hierarchy of one periodic cell (vfem_hom_mg_*) */
 typedef struct vfem_gmg vfem_gmg;     /* MultigridSolver<p,..,p> of the generic path */
+typedef struct vfem_thermal_mg vfem_thermal_mg; /* the multigrid hierarchy of one heat-conduction problem (vfem_thermal_mg_*) */
 
 const char *vfem_last_error(void);
 int  vfem_device_count(void);                 /* number of visible HIP devices (0 => no GPU) */
@@ -720,6 +721,46 @@ int vfem_thermal_gradient(int dim, const int64_t *nelems_host, int ncols, const 
                           const double *dkappa, const double *A, const double *B, double *g, void *stream);
 int vfem_thermal_flux(int dim, const int64_t *nelems_host, const double *h_host, const double *k_host, const double *kappa,
                       const double *T, double *flux, void *stream);
+
+/* ---- multigrid-preconditioned CG for the scalar conduction operator ----
+ * vfem_thermal_mg_create builds the hierarchy of one grid, one set of element multipliers and one mask from the arguments of
+ * vfem_thermal_apply; the handle keeps the pointers kappa and fixed (device; fixed may be NULL), which must stay valid and
+ * unchanged until vfem_thermal_mg_destroy.  Level 0 is the grid (matrix-free from kappa); level l + 1 exists while every extent of
+ * level l is even and at least 4 elements and max_coarsenings (negative: no limit) allows it, and has half the elements per axis.
+ * A coarse node is fixed exactly when the fine node it coincides with is.  With I_l the N-linear interpolation and F_l the 0/1
+ * diagonal of the free nodes, P_l = F_l I_l F_{l+1},  A'_0 = F_0 (sum_e kappa[e] Kc0) F_0,  A'_{l+1} = P_l^T A'_l P_l,
+ * A_l = A'_l + (I - F_l); levels >= 1 store A'_l as a 3^dim-point stencil.  The coarsest level is inverted densely and may have at
+ * most 40 000 nodes: create fails with a message that lists the level sizes otherwise, before anything large is allocated, and with
+ * "breakdown at the coarsest level ..." when that matrix is not positive definite (a singular operator).  A grid with an odd
+ * extent is a one-level hierarchy, whose cycle is the exact inverse.  Create synchronises the stream.
+ * vfem_thermal_mg_level_dims: n_out[dim] = elements per axis of level l.  vfem_thermal_mg_bytes: device memory the handle holds.
+ * vfem_thermal_mg_level_fixed: fixed_out (device, one byte per node of level l) = the level's mask, 0 or 1.
+ * vfem_thermal_mg_level_apply: Y = A_l X on the nodes of level l.
+ * vfem_thermal_mg_smooth: one sweep of A_l X = B on X over the 2^dim colours (the parity of the node index per axis, axis 0 the most
+ *   significant bit), ascending (forward) or descending: x += (b - A_l x) / diag A_l on every node of the colour.
+ * vfem_thermal_mg_restrict: coarse (level l + 1) = P_l^T fine (level l).  vfem_thermal_mg_prolong_add: fine += P_l coarse; fixed fine
+ *   nodes are not written.
+ * vfem_thermal_mg_vcycle: X = V-cycle(B) on level 0 from a zero iterate: `smoothing` ascending sweeps, the residual, the coarse
+ *   correction, `smoothing` descending sweeps; the coarsest level is solved exactly.  A symmetric positive definite operator.
+ * vfem_thermal_mg_pcg: vfem_thermal_pcg with z = V-cycle(r) as the preconditioner; the same stopping rule, outputs and two errors,
+ *   but the host reads the residual after every iteration, so the count it returns is exact.  Synchronises the stream.
+ * All gathers in a fixed order, no atomics: bit-identical run to run.  Device pointers need 8-byte alignment only.
+ * Refused before any device call: a NULL handle or pointer, a level out of range (restrict and prolong_add: l + 1 must exist),
+ * smoothing outside [1, 16], tol <= 0, max_iter < 1, an output that overlaps its input, and at create what vfem_thermal_apply refuses. */
+int vfem_thermal_mg_create(vfem_thermal_mg **out, int dim, const int64_t *nelems_host, const double *Kc0_host, const double *kappa,
+                           const uint8_t *fixed, int max_coarsenings, void *stream);
+int vfem_thermal_mg_destroy(vfem_thermal_mg *h);
+int vfem_thermal_mg_num_levels(vfem_thermal_mg *h);
+int64_t vfem_thermal_mg_bytes(vfem_thermal_mg *h);
+int vfem_thermal_mg_level_dims(vfem_thermal_mg *h, int l, int64_t *n_out);
+int vfem_thermal_mg_level_fixed(vfem_thermal_mg *h, int l, uint8_t *fixed_out, void *stream);
+int vfem_thermal_mg_level_apply(vfem_thermal_mg *h, int l, const double *X, double *Y, void *stream);
+int vfem_thermal_mg_smooth(vfem_thermal_mg *h, int l, double *X, const double *B, int forward, void *stream);
+int vfem_thermal_mg_restrict(vfem_thermal_mg *h, int l, const double *fine, double *coarse, void *stream);
+int vfem_thermal_mg_prolong_add(vfem_thermal_mg *h, int l, const double *coarse, double *fine, void *stream);
+int vfem_thermal_mg_vcycle(vfem_thermal_mg *h, const double *B, double *X, int smoothing, void *stream);
+int vfem_thermal_mg_pcg(vfem_thermal_mg *h, const double *b, double *x, double tol, int max_iter, int smoothing,
+                        int *iterations_out_host, double *relres_out_host, void *stream);
 
 /* ---- timers: BENCHMARK_* registry (MeshFEM GlobalBenchmark.hh / Timer.hh; VoxelFEM.cc:245-255) ---- */
 int vfem_timers_reset(void);

@@ -239,6 +239,18 @@ SIGNATURES = {
     "vfem_thermal_gradient": (c_int, _THERMAL + [c_int, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p,
                                                  c_void_p]),
     "vfem_thermal_flux": (c_int, _THERMAL + [POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vfem_thermal_mg_create": (c_int, [POINTER(c_void_p)] + _THERMAL + [POINTER(c_double), c_void_p, c_void_p, c_int, c_void_p]),
+    "vfem_thermal_mg_destroy": (c_int, [c_void_p]),
+    "vfem_thermal_mg_num_levels": (c_int, [c_void_p]),
+    "vfem_thermal_mg_bytes": (c_int64, [c_void_p]),
+    "vfem_thermal_mg_level_dims": (c_int, [c_void_p, c_int, POINTER(c_int64)]),
+    "vfem_thermal_mg_level_fixed": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "vfem_thermal_mg_level_apply": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "vfem_thermal_mg_smooth": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "vfem_thermal_mg_restrict": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "vfem_thermal_mg_prolong_add": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "vfem_thermal_mg_vcycle": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "vfem_thermal_mg_pcg": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int, c_int, POINTER(c_int), POINTER(c_double), c_void_p]),
     "vfem_timers_reset": (c_int, []),
     "vfem_timers_report": (c_int, [c_char_p, c_size_t]),
 }

@@ -15,9 +15,7 @@
 // against 2.23 ms.  The solver applies one column, so the predicated form stays)
 //
 // Gradient and flux: one thread per ELEMENT; the 2^N nodal values of a column are loaded once.
-#include "thermal.h"
-
-#include "cell_threads.h"
+#include "thermal_device.h"
 
 #include <algorithm>
 
@@ -25,58 +23,21 @@ namespace vfem {
 
 namespace {
 
-template <int N>
-struct ThermalTraits {
-    static constexpr int NPE = 1 << N;
-    static constexpr int NB = N == 2 ? 9 : 27;          // nodes coupled to a node
-    static constexpr int SELF = (NB - 1) / 2;
-};
-
-// kappa of the element in which the node at c is local node el; 0 outside the grid
-template <int N>
-__device__ __forceinline__ double incident_kappa(const ModalGrid &g, const double *__restrict__ kappa, const int (&c)[N], int el) {
-    int ec[N];
-    bool in = true;
-#pragma unroll
-    for (int d = 0; d < N; ++d) {
-        ec[d] = c[d] - node_bit<N>(el, d);
-        in = in && ec[d] >= 0 && ec[d] < g.ne[d];
-    }
-    return in ? kappa[flat_index<N>(g.ne, 0, ec)] : 0.0;
-}
-
+// (the node's couplings and the neighbours that take part: thermal_device.h, shared with the multigrid kernels; expanded here as
+// macros, which keeps this kernel's registers where they were)
 template <int N>
 __global__ void __launch_bounds__(256) k_thermal_apply(ModalGrid g, ThermalMatrix K, const double *__restrict__ kappa,
                                                        const uint8_t *__restrict__ fixed, int ncols, const double *__restrict__ X,
                                                        const double *__restrict__ b, double *__restrict__ Y) {
-    constexpr int NPE = ThermalTraits<N>::NPE, NB = ThermalTraits<N>::NB, SELF = ThermalTraits<N>::SELF;
+    constexpr int NB = ThermalTraits<N>::NB, SELF = ThermalTraits<N>::SELF;
     int c[N];
     if (!thread_cell<N>(g.ne, 1, c)) return;
     const long long node = flat_index<N>(g.ne, 1, c);
     double coef[NB];
-#pragma unroll
-    for (int k = 0; k < NB; ++k) coef[k] = 0.0;
-#pragma unroll
-    for (int el = 0; el < NPE; ++el) {
-        const double ke = incident_kappa<N>(g, kappa, c, el);
-#pragma unroll
-        for (int j = 0; j < NPE; ++j) coef[neighbour_of<N>(el, j)] = fma(ke, K.k[el * NPE + j], coef[neighbour_of<N>(el, j)]);
-    }
+    VFEM_THERMAL_COUPLINGS(N, g, K, kappa, c, coef);
     long long delta[NB];            // the neighbour's node index minus this one's
     unsigned live = 0u;             // neighbours inside the grid that are not fixed
-#pragma unroll
-    for (int k = 0; k < NB; ++k) {
-        bool in = true;
-        long long off = 0;
-#pragma unroll
-        for (int d = 0; d < N; ++d) {
-            const int o = neighbour_offset<N>(k, d);
-            in = in && c[d] + o >= 0 && c[d] + o <= g.ne[d];
-            off = off * (g.ne[d] + 1) + o;
-        }
-        delta[k] = off;
-        if (in && !(fixed && fixed[node + off])) live |= 1u << k;
-    }
+    VFEM_THERMAL_LIVE_NEIGHBOURS(N, g, fixed, c, node, delta, live);
     const bool self_fixed = !((live >> SELF) & 1u);
     for (int col = 0; col < ncols; ++col) {
         const double *__restrict__ x = X + col * g.nnode + node;

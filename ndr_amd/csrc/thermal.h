@@ -8,6 +8,9 @@
 #pragma once
 #include "modal.h"
 
+#include <functional>
+#include <string>
+
 namespace vfem {
 
 constexpr int THERMAL_MAX_COLS = 8;
@@ -50,5 +53,17 @@ void launch_thermal_scale(long long n, const double *dinv, const double *r, doub
 // which p.Ap stopped being positive (0: none), [6] that p.Ap, [7] r.r then).  Stage 1 (after p.Ap) records a breakdown; from then
 // on both stages make the step and the direction update neutral (alpha = 0, beta = 0), so the loop idles until the host looks.
 void launch_thermal_pcg_guard(double *sc, int stage, int iteration, hipStream_t s);
+
+// Host code of thermal.hip that thermal_mg.hip uses too.  The argument checks every vfem_thermal_* call starts with (w: the entry
+// point's name for the message):
+ModalGrid thermal_grid(const std::string &w, int dim, const int64_t *nelems_host);
+ThermalMatrix thermal_element_matrix(const std::string &w, int dim, const double *Kc0_host);
+// The PCG loop of vfem_thermal_pcg and vfem_thermal_mg_pcg on A x = b from the x given: z = M^-1 r is the caller's (launched on s);
+// the host reads the scalars before the first iteration and then every look_every iterations, stops when |r| / |b| <= tol, and
+// throws "not converged after ..." or "breakdown at iteration ..." with the residual.  The outputs are written in every case.
+using ThermalPreconditioner = std::function<void(const double *r, double *z)>;
+void thermal_pcg(const std::string &w, const ModalGrid &g, const ThermalMatrix &K, const double *kappa, const uint8_t *fixed,
+                 const double *b, double *x, double tol, int max_iter, int look_every, const ThermalPreconditioner &precondition,
+                 int *iterations_out_host, double *relres_out_host, hipStream_t s);
 
 }  // namespace vfem

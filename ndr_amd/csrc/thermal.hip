@@ -70,6 +70,79 @@ void check_output(const std::string &w, const char *name, const ModalGrid &g, co
 
 }  // namespace
 
+namespace vfem {
+
+ModalGrid thermal_grid(const std::string &w, int dim, const int64_t *nelems) { return thermal_setup(w, dim, nelems, nullptr); }
+ThermalMatrix thermal_element_matrix(const std::string &w, int dim, const double *Kc0) { return thermal_matrix(w, dim, Kc0); }
+
+void thermal_pcg(const std::string &w, const ModalGrid &g, const ThermalMatrix &K, const double *kappa, const uint8_t *fixed,
+                 const double *b, double *x, double tol, int max_iter, int look_every, const ThermalPreconditioner &precondition,
+                 int *iterations_out_host, double *relres_out_host, hipStream_t s) {
+    const long long n = g.nnode;
+    *iterations_out_host = 0;
+    *relres_out_host = 0.0;
+
+    DevBuf<double> vec, sc, scratch;
+    vec.alloc((size_t) 4 * n);
+    sc.alloc(8);
+    scratch.alloc(REDUCE_SCRATCH_DOUBLES);
+    sc.zero(s);
+    double *r = vec.p, *z = r + n, *d = z + n, *Ad = d + n;
+    double host[8];
+    auto read = [&]() {
+        VFEM_HIP(hipMemcpyAsync(host, sc.p, sizeof host, hipMemcpyDeviceToHost, s));
+        VFEM_HIP(hipStreamSynchronize(s));
+    };
+    launch_dot(n, b, b, scratch.p, sc.p + 4, s);
+    launch_thermal_apply(g, K, kappa, fixed, 1, x, b, r, s);            // r = b - A x
+    launch_dot(n, r, r, scratch.p, sc.p + 3, s);
+    read();
+    const double bb = host[4];
+    double rr = host[3];
+    if (bb == 0.0) {                                                    // A is positive definite: the solution is zero
+        VFEM_HIP(hipMemsetAsync(x, 0, (size_t) n * sizeof(double), s));
+        VFEM_HIP(hipStreamSynchronize(s));
+        return;
+    }
+    int it = 0;
+    bool done = rr <= tol * tol * bb;
+    char msg[512];
+    while (!done && it < max_iter) {
+        ++it;
+        launch_shift_scalar(sc.p, s);                                   // the last r.z
+        precondition(r, z);
+        launch_dot(n, r, z, scratch.p, sc.p, s);
+        launch_thermal_pcg_guard(sc.p, 0, it, s);
+        launch_pcg_direction(n, z, d, sc.p, it == 1, s);
+        launch_thermal_apply(g, K, kappa, fixed, 1, d, nullptr, Ad, s);
+        launch_dot(n, d, Ad, scratch.p, sc.p + 2, s);
+        launch_thermal_pcg_guard(sc.p, 1, it, s);
+        launch_pcg_step_dot(n, x, r, d, Ad, sc.p, scratch.p, sc.p + 3, s);
+        if (it % look_every == 0 || it == max_iter) {
+            read();
+            rr = host[3];
+            if (host[5] != 0.0) {
+                *iterations_out_host = (int) host[5];
+                *relres_out_host = std::sqrt(host[7] / bb);
+                snprintf(msg, sizeof msg, "%s: breakdown at iteration %d: p . Ap = %.3e is not positive (|r|/|b| = %.3e, tol %.3e); the "
+                         "operator is singular: no fixed node, a free node whose incident elements all have zero conductivity, or "
+                         "non-finite data", w.c_str(), (int) host[5], host[6], *relres_out_host, tol);
+                throw Error(msg);
+            }
+            done = rr <= tol * tol * bb;
+            if (!(rr == rr)) break;
+        }
+    }
+    *iterations_out_host = it;
+    *relres_out_host = std::sqrt(rr / bb);
+    if (!done) {
+        snprintf(msg, sizeof msg, "%s: not converged after %d iterations: |r|/|b| = %.3e (tol %.3e)", w.c_str(), it, *relres_out_host, tol);
+        throw Error(msg);
+    }
+}
+
+}  // namespace vfem
+
 extern "C" {
 
 int vfem_thermal_apply(int dim, const int64_t *nelems_host, const double *Kc0_host, const double *kappa, const uint8_t *fixed,
@@ -140,67 +213,11 @@ int vfem_thermal_pcg(int dim, const int64_t *nelems_host, const double *Kc0_host
     const long long n = g.nnode;
     if (overlaps(x, n, b, n)) throw Error(w + ": x aliases b");
     check_output(w, "x", g, x, n, kappa, fixed);
-    *iterations_out_host = 0;
-    *relres_out_host = 0.0;
-
-    DevBuf<double> vec, sc, scratch;
-    vec.alloc((size_t) 5 * n);
-    sc.alloc(8);
-    scratch.alloc(REDUCE_SCRATCH_DOUBLES);
-    sc.zero(s);
-    double *r = vec.p, *z = r + n, *d = z + n, *Ad = d + n, *dinv = Ad + n;
-    double host[8];
-    auto read = [&]() {
-        VFEM_HIP(hipMemcpyAsync(host, sc.p, sizeof host, hipMemcpyDeviceToHost, s));
-        VFEM_HIP(hipStreamSynchronize(s));
-    };
-    launch_thermal_diagonal(g, K, kappa, fixed, 1, dinv, s);
-    launch_dot(n, b, b, scratch.p, sc.p + 4, s);
-    launch_thermal_apply(g, K, kappa, fixed, 1, x, b, r, s);            // r = b - A x
-    launch_dot(n, r, r, scratch.p, sc.p + 3, s);
-    read();
-    const double bb = host[4];
-    double rr = host[3];
-    if (bb == 0.0) {                                                    // A is positive definite: the solution is zero
-        VFEM_HIP(hipMemsetAsync(x, 0, (size_t) n * sizeof(double), s));
-        VFEM_HIP(hipStreamSynchronize(s));
-        return 0;
-    }
-    int it = 0;
-    bool done = rr <= tol * tol * bb;
-    char msg[512];
-    while (!done && it < max_iter) {
-        ++it;
-        launch_shift_scalar(sc.p, s);                                   // the last r.z
-        launch_thermal_scale(n, dinv, r, z, s);
-        launch_dot(n, r, z, scratch.p, sc.p, s);
-        launch_thermal_pcg_guard(sc.p, 0, it, s);
-        launch_pcg_direction(n, z, d, sc.p, it == 1, s);
-        launch_thermal_apply(g, K, kappa, fixed, 1, d, nullptr, Ad, s);
-        launch_dot(n, d, Ad, scratch.p, sc.p + 2, s);
-        launch_thermal_pcg_guard(sc.p, 1, it, s);
-        launch_pcg_step_dot(n, x, r, d, Ad, sc.p, scratch.p, sc.p + 3, s);
-        if (it % THERMAL_PCG_CHECK == 0 || it == max_iter) {
-            read();
-            rr = host[3];
-            if (host[5] != 0.0) {
-                *iterations_out_host = (int) host[5];
-                *relres_out_host = std::sqrt(host[7] / bb);
-                snprintf(msg, sizeof msg, "%s: breakdown at iteration %d: p . Ap = %.3e is not positive (|r|/|b| = %.3e, tol %.3e); the "
-                         "operator is singular: no fixed node, a free node whose incident elements all have zero conductivity, or "
-                         "non-finite data", w.c_str(), (int) host[5], host[6], *relres_out_host, tol);
-                throw Error(msg);
-            }
-            done = rr <= tol * tol * bb;
-            if (!(rr == rr)) break;
-        }
-    }
-    *iterations_out_host = it;
-    *relres_out_host = std::sqrt(rr / bb);
-    if (!done) {
-        snprintf(msg, sizeof msg, "%s: not converged after %d iterations: |r|/|b| = %.3e (tol %.3e)", w.c_str(), it, *relres_out_host, tol);
-        throw Error(msg);
-    }
+    DevBuf<double> dinv;
+    dinv.alloc((size_t) n);
+    launch_thermal_diagonal(g, K, kappa, fixed, 1, dinv.p, s);
+    const ThermalPreconditioner jacobi = [&](const double *r, double *z) { launch_thermal_scale(n, dinv.p, r, z, s); };
+    thermal_pcg(w, g, K, kappa, fixed, b, x, tol, max_iter, THERMAL_PCG_CHECK, jacobi, iterations_out_host, relres_out_host, s);
     VFEM_CATCH
 }
 

@@ -75,7 +75,9 @@ class HeatConductionSimulator:
     element ([numElements] or a scalar).
 
     ``solve_device(Q)`` factorises the band of A on the device (``vfem_thermal_band_assemble`` + ``vfem_band_spd_factor``) and keeps
-    the factor until the densities, the material or the mask change; ``pcg_device`` is the Jacobi-preconditioned CG."""
+    the factor until the densities, the material or the mask change; ``pcg_device`` is the conjugate-gradient solver, with the
+    Jacobi preconditioner or (``preconditioner="multigrid"``) a geometric multigrid V-cycle whose hierarchy (``vfem_thermal_mg_*``)
+    is kept as long as the factor is: ``numMultigridBuilds()``, ``multigridLevels()``, ``multigridBytes()``."""
 
     def __init__(self, domainBBox, elementsPerDimension):
         _lib.require_gpu()
@@ -98,6 +100,8 @@ class HeatConductionSimulator:
         self._Kc0 = None
         self._band = None                   # the kept factor
         self._factorizations = 0
+        self._mg = None                     # the kept multigrid hierarchy: (handle, kappa, mask, Kc0), the arrays it reads kept alive
+        self._mg_builds = 0
         self.last_iterations = 0
         self.last_relative_residual = 0.0
 
@@ -120,8 +124,20 @@ class HeatConductionSimulator:
         return self.N, self._ne.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
 
     def _changed(self):
-        """the operator changed: the kept factor no longer stands for it"""
+        """the operator changed: the kept factor and the kept hierarchy no longer stand for it"""
         self._band = None
+        self._drop_multigrid()
+
+    def _drop_multigrid(self):
+        if getattr(self, "_mg", None) is not None:
+            handle, self._mg = self._mg[0], None
+            _lib.load().vfem_thermal_mg_destroy(handle)
+
+    def __del__(self):
+        try:
+            self._drop_multigrid()
+        except Exception:
+            pass
 
     # ---- material ----
     def _get_conductivity(self):
@@ -317,22 +333,60 @@ class HeatConductionSimulator:
         return _to_np(self.solve_device(Q))
 
     # ---- iterative solver ----
-    def pcg_device(self, Q, x0=None, tol=1e-8, maxIter=2000):
-        """Jacobi-preconditioned CG on A T = Q from ``x0`` (default 0) until |r| / |Q| <= tol; ``last_iterations`` and
-        ``last_relative_residual`` are those of this solve.  Raises when ``maxIter`` is reached or the operator is singular."""
+    def _multigrid(self):
+        """the hierarchy of the present operator (``vfem_thermal_mg_create``), built on first use and kept until the densities, the
+        material or the mask change: the events that drop the band factor"""
+        if self._mg is None:
+            kappa = self.elementConductivities_device()[0]
+            mask, Kc0 = self._mask_dev, self._K()
+            handle = ctypes.c_void_p()
+            _lib.check(_lib.load().vfem_thermal_mg_create(ctypes.byref(handle), *self._head(), _dp(Kc0), _ptr(kappa),
+                                                          _ptr(mask) if self._mask.any() else None, -1, _stream()))
+            self._mg = (handle, kappa, mask, Kc0)
+            self._mg_builds += 1
+        return self._mg[0]
+
+    def numMultigridBuilds(self):
+        return self._mg_builds
+
+    def multigridLevels(self):
+        """the elements per axis of every level of the hierarchy (built if need be)"""
+        lib, h = _lib.load(), self._multigrid()
+        out = []
+        for l in range(lib.vfem_thermal_mg_num_levels(h)):
+            n = np.zeros(self.N, dtype=np.int64)
+            _lib.check(lib.vfem_thermal_mg_level_dims(h, l, n.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+            out.append([int(v) for v in n])
+        return out
+
+    def multigridBytes(self):
+        """device memory the hierarchy holds (built if need be)"""
+        return int(_lib.load().vfem_thermal_mg_bytes(self._multigrid()))
+
+    def pcg_device(self, Q, x0=None, tol=1e-8, maxIter=2000, preconditioner="jacobi", smoothing=1):
+        """conjugate gradients on A T = Q from ``x0`` (default 0) until |r| / |Q| <= tol, with the Jacobi preconditioner or
+        (``preconditioner="multigrid"``) one V-cycle of ``smoothing`` sweeps before and after the coarse correction;
+        ``last_iterations`` and ``last_relative_residual`` are those of this solve.  Raises when ``maxIter`` is reached or the
+        operator is singular."""
+        if preconditioner not in ("jacobi", "multigrid"):
+            raise RuntimeError("pcg_device: preconditioner is \"jacobi\" or \"multigrid\" (got %r)" % (preconditioner,))
         self._need_sink("pcg_device")
         Q = _to_dev(Q, (self.numNodes(),))
         x = torch.zeros_like(Q) if x0 is None else _to_dev(x0, (self.numNodes(),)).clone()
-        kappa = self.elementConductivities_device()[0]
         it, rel = ctypes.c_int(0), ctypes.c_double(0.0)
-        status = _lib.load().vfem_thermal_pcg(*self._head(), _dp(self._K()), _ptr(kappa), self._fixed(), _ptr(Q), _ptr(x), float(tol),
-                                              int(maxIter), ctypes.byref(it), ctypes.byref(rel), _stream())
+        if preconditioner == "multigrid":
+            status = _lib.load().vfem_thermal_mg_pcg(self._multigrid(), _ptr(Q), _ptr(x), float(tol), int(maxIter), int(smoothing),
+                                                     ctypes.byref(it), ctypes.byref(rel), _stream())
+        else:
+            kappa = self.elementConductivities_device()[0]
+            status = _lib.load().vfem_thermal_pcg(*self._head(), _dp(self._K()), _ptr(kappa), self._fixed(), _ptr(Q), _ptr(x), float(tol),
+                                                  int(maxIter), ctypes.byref(it), ctypes.byref(rel), _stream())
         self.last_iterations, self.last_relative_residual = int(it.value), float(rel.value)
         _lib.check(status)
         return x
 
-    def pcg(self, Q, x0=None, tol=1e-8, maxIter=2000):
-        return _to_np(self.pcg_device(Q, x0, tol, maxIter))
+    def pcg(self, Q, x0=None, tol=1e-8, maxIter=2000, preconditioner="jacobi", smoothing=1):
+        return _to_np(self.pcg_device(Q, x0, tol, maxIter, preconditioner, smoothing))
 
     # ---- fields ----
     def flux_device(self, T):
@@ -363,21 +417,28 @@ class ThermalComplianceObjective:
     """J(rho) = Q . T with A(rho) T = Q: the thermal compliance of a ``HeatConductionSimulator``, and dJ/drho_e = -kappa'_e T_e^T Kc0
     T_e (self-adjoint: no adjoint solve; nowhere positive, so ``OCOptimizer`` applies).
 
-    ``solver``: "direct" (``heat.solve_device``: one factorisation per design) or "pcg" (``heat.pcg_device`` with the attributes
+    ``solver``: "direct" (``heat.solve_device``: one factorisation per design), "pcg" (``heat.pcg_device`` with the attributes
     ``tol`` = 1e-8 and ``maxIter`` = 2000, warm-started from the last temperature; ``iterations`` is the count of the last
-    solve).  The sources are read from the simulator at every update.  The constructor solves once unless ``skipSolve``.
+    solve).  ``preconditioner`` (with "pcg"): "jacobi", or "multigrid" with the attribute ``smoothing`` = 1: one hierarchy per design,
+    which the adjoint solves of the measures built on this objective reuse.  (``solver`` itself keeps its two values: "multigrid"
+    as a solver name stays refused, as it was.)  The sources are read from the simulator at every update.  The constructor solves
+    once unless ``skipSolve``.
 
     The objective protocol of the design loop: ``updateCache(xPhys)``, ``evaluate()``, ``gradient_device()``, ``gradient()``.
     ``_sim`` is the simulator and ``_u`` the temperature, a new tensor with every solve (what ``mma.ObjectiveConstraint``
     follows)."""
 
-    def __init__(self, heat, solver="direct", skipSolve=False):
+    def __init__(self, heat, solver="direct", skipSolve=False, preconditioner="jacobi"):
         if not isinstance(heat, HeatConductionSimulator):
             raise TypeError("ThermalComplianceObjective takes a HeatConductionSimulator (got %r)" % (type(heat).__name__,))
         if solver not in ("direct", "pcg"):
             raise RuntimeError("ThermalComplianceObjective: solver is \"direct\" or \"pcg\" (got %r)" % (solver,))
-        self._sim, self.solver = heat, solver
-        self.tol, self.maxIter = 1e-8, 2000
+        if preconditioner not in ("jacobi", "multigrid"):
+            raise RuntimeError("ThermalComplianceObjective: preconditioner is \"jacobi\" or \"multigrid\" (got %r)" % (preconditioner,))
+        if preconditioner != "jacobi" and solver != "pcg":
+            raise RuntimeError("ThermalComplianceObjective: a preconditioner goes with solver=\"pcg\" (got solver %r)" % (solver,))
+        self._sim, self.solver, self.preconditioner = heat, solver, preconditioner
+        self.tol, self.maxIter, self.smoothing = 1e-8, 2000, 1
         self.iterations = 0
         self._u = self._f = None
         self._J = self._grad = None
@@ -388,7 +449,7 @@ class ThermalComplianceObjective:
         """A^-1 Q through the objective's solver (the adjoint solves of the measures built on it come here too)"""
         if self.solver == "direct":
             return self._sim.solve_device(Q)
-        x = self._sim.pcg_device(Q, last, self.tol, self.maxIter)
+        x = self._sim.pcg_device(Q, last, self.tol, self.maxIter, self.preconditioner, self.smoothing)
         self.iterations = self._sim.last_iterations
         return x
 
