@@ -329,6 +329,7 @@ class GenericMG:
         b_norm_sq = float(np.sum(b * b))
         r = self.residual(0, x, b)
         rMr, d, i = 0.0, None, 0
+        self.relres_history = []                                      # relative residual after every iteration
         while i < max_iter and float(np.sum(r * r)) > tol * tol * b_norm_sq:
             i += 1
             s = self.apply_preconditioner_inv(r, mg_iterations, mg_smoothing, fmg)
@@ -340,6 +341,7 @@ class GenericMG:
             alpha = rMr / float(np.sum(d * Ad))
             x += alpha * d
             r -= alpha * Ad
+            self.relres_history.append(float(np.sqrt(np.sum(r * r) / b_norm_sq)))
         self.last_iters = i
         self.last_relres = float(np.sqrt(np.sum(r * r) / b_norm_sq)) if b_norm_sq > 0 else 0.0
         return x
