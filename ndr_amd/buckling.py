@@ -18,23 +18,18 @@ values.  The numerics run in ``libvfem.so`` (``vfem_buckling_*``, ``vfem_modal_p
     K_G phi = nu K phi on the free components, phi^T K phi = 1;  the wanted modes have the lowest (most negative) nu,  lambda = -1 / nu
     J = (sum_{i <= k} mu_i^P)^(1/P),  mu_i = 1 / lambda_i = -nu_i:  1 / J <= lambda_1, so  J <= bound  caps the critical load from below
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib, modal
+from ._grid import ObjectiveFunction, _dp, simp_multipliers
 from .pyVoxelFEM import _dev, _ptr, _stream, _to_np
-from .stress import _Grid as _StressGrid
+from .stress import _Grid as _StressGrid, _exponent
 
 __all__ = ["geometricMultipliers", "applyKG", "applyKG_device", "bucklingModes", "BucklingObjective", "BucklingFunction",
            "bucklingMeasure", "MAX_MODES"]
 
 MAX_MODES = modal.MAX_MODES
-
-
-def _dp(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
 class _Grid(_StressGrid):
@@ -44,17 +39,14 @@ class _Grid(_StressGrid):
     def __init__(self, sim):
         super().__init__(sim)
         self.blocks = modal._Grid(sim)
-        self.n, self.mask, self.fixed = self.blocks.n, self.blocks.mask, self.blocks.fixed
+        self.n = self.blocks.n
+
+    mask = property(lambda s: s.blocks.mask)            # one upload for both
 
     def multipliers(self, stressExponent):
         """(mG, dmG/drho) of the simulator's densities: mG = rho^q E_0"""
         sim = self.sim
-        q = float(sim.gamma if stressExponent is None else stressExponent)
-        if not q > 0.0:
-            raise RuntimeError("stressExponent must be positive (got %r)" % (stressExponent,))
-        rho = sim.getDensities_device()[:self.nelem]
-        E0 = float(sim.E_0)
-        return (rho ** q * E0).contiguous(), (q * rho ** (q - 1.0) * E0).contiguous()
+        return simp_multipliers(sim, sim.getDensities_device()[:self.nelem], _exponent(sim, stressExponent), 0.0)
 
     def geom_apply(self, mG, u, X, Y, masked=True):
         _lib.check(_lib.load().vfem_buckling_geom_apply(*self.head(), _ptr(mG), _ptr(u), _ptr(self.mask) if masked else None,
@@ -267,9 +259,7 @@ class BucklingObjective:
         if st["grad"] is None:
             g, sim = st["grid"], self._sim
             v = self.adjoint_device()
-            rho = sim.getDensities_device()[:g.nelem]
-            gamma = float(sim.gamma)
-            dE = (gamma * rho ** (gamma - 1.0) * (float(sim.E_0) - float(sim.E_min))).contiguous()
+            dE = simp_multipliers(sim, sim.getDensities_device()[:g.nelem])[1]
             dmG = g.multipliers(self.stressExponent)[1]
             K0 = np.ascontiguousarray(sim.fullDensityElementStiffnessMatrix())
             cG, cK = np.ascontiguousarray(-st["w"]), np.ascontiguousarray(st["w"] * st["nu"])
@@ -283,24 +273,12 @@ class BucklingObjective:
         return _to_np(self.gradient_device())
 
 
-class BucklingFunction(torch.autograd.Function):
+class BucklingFunction(ObjectiveFunction):
     """J of the predicted densities as an autograd node, the counterpart of ``modal.MeanEigenvalueFunction``: forward sets the
     densities, solves the load case and the eigenproblem; backward is ``gradient_device()`` weighted by the incoming gradient."""
 
-    @staticmethod
-    def forward(ctx, densities, objective):
-        objective.updateCache(densities.detach().reshape(-1))
-        J = objective.evaluate()
-        ctx.objective, ctx.u, ctx.dtype, ctx.shape = objective, objective.solved._u, densities.dtype, densities.shape
-        return torch.tensor(J, dtype=torch.float64, device=densities.device)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        obj = ctx.objective
-        if obj.solved._u is not ctx.u:
-            raise RuntimeError("bucklingMeasure: the objective was updated between forward and backward")
-        g = float(grad_output.detach().cpu()) * obj.gradient_device()
-        return g.to(ctx.dtype).reshape(ctx.shape), None
+    NAME = "bucklingMeasure"
+    field = staticmethod(lambda objective: objective.solved._u)
 
 
 def bucklingMeasure(densities, objective):

@@ -1,6 +1,7 @@
 // The linearised-buckling entry points of include/vfem.h (vfem_buckling_*).  Handle-free: every call takes the grid, the
 // voxel's edge lengths and the flattened tensor.  Every argument is checked before the first device call.
 #include "buckling.h"
+#include "grid_args.h"
 #include "vfem_host.h"
 
 #include <cmath>
@@ -11,36 +12,6 @@
 using namespace vfem;
 
 namespace {
-
-ModalGrid buckling_setup(const std::string &w, int dim, const int64_t *nelems, const double *h, const double *D) {
-    if (dim != 2 && dim != 3) throw Error(w + ": dim must be 2 or 3");
-    if (!nelems || !h || !D) throw Error(w + ": null argument");
-    ModalGrid g;
-    g.N = dim;
-    g.ne[2] = 1;
-    g.h[2] = 1.0;
-    g.nelem = g.nnode = 1;
-    for (int d = 0; d < dim; ++d) {
-        if (nelems[d] < 1) throw Error(w + ": every extent must be at least 1 element");
-        if (nelems[d] > (1 << 27)) throw Error(w + ": grid too large");
-        if (!(h[d] > 0.0) || !std::isfinite(h[d])) throw Error(w + ": the voxel's edge lengths must be positive");
-        g.ne[d] = (int) nelems[d];
-        g.h[d] = h[d];
-        g.nelem *= nelems[d];
-        g.nnode *= nelems[d] + 1;
-        if (g.nnode > (1LL << 31)) throw Error(w + ": grid too large (more than 2^31 nodes)");
-    }
-    const int S = dim == 2 ? 3 : 6;
-    for (int i = 0; i < S * S; ++i)
-        if (!std::isfinite(D[i])) throw Error(w + ": the tensor is not finite");
-    return g;
-}
-
-void check_count(const std::string &w, const char *what, int k, int most) {
-    if (k < 1 || k > most) throw Error(w + ": " + what + " must be 1 to " + std::to_string(most) + " (got " + std::to_string(k) + ")");
-}
-
-bool overlaps(const double *a, int64_t na, const double *b, int64_t nb) { return a < b + nb && b < a + na; }
 
 // T[j][n][m] = int_e grad N_n^T (C : B_j(x)) grad N_m dV by 2 Gauss points per axis (exact: degree <= 3 per axis); D is the
 // flattened tensor of ndr_amd.materials (xx yy xy / xx yy zz yz xz xy, TENSOR components: the shear strains count twice).
@@ -91,18 +62,6 @@ std::vector<double> geometric_table(int N, const double *h, const double *D) {
         for (int n = 0; n < npe; ++n)
             for (int m = 0; m < n; ++m) T[((size_t) j * npe + n) * npe + m] = T[((size_t) j * npe + m) * npe + n];
     return T;
-}
-
-bool overlaps_bytes(const void *a, int64_t na, const void *b, int64_t nb) {
-    const char *pa = (const char *) a, *pb = (const char *) b;
-    return pa < pb + nb && pb < pa + na;
-}
-
-// an output of `len` doubles against the element multipliers and the node mask (which may be null)
-void check_output(const std::string &w, const char *name, const double *out, int64_t len, const ModalGrid &g, const double *mult,
-                  const uint8_t *mask) {
-    if (overlaps(out, len, mult, g.nelem)) throw Error(w + ": " + name + " aliases the multipliers");
-    if (mask && overlaps_bytes(out, len * (int64_t) sizeof(double), mask, g.nnode)) throw Error(w + ": " + name + " aliases the mask");
 }
 
 // The table on the device.  It depends on (device, dim, h, D) only, so it is formed and uploaded once per such key and kept for the
@@ -161,13 +120,13 @@ int vfem_buckling_geom_apply(int dim, const int64_t *nelems_host, const double *
     VFEM_TRY
     const std::string w = "vfem_buckling_geom_apply";
     hipStream_t s = S(stream);
-    const ModalGrid g = buckling_setup(w, dim, nelems_host, h_host, D_host);
+    const ModalGrid g = grid_and_tensor_args(w, dim, nelems_host, h_host, D_host);
     if (!mG || !u || !X || !Y) throw Error(w + ": null argument");
     check_count(w, "ncols", ncols, BLOCK_MAX_COLS);
     const int64_t one = g.nnode * g.N, len = (int64_t) ncols * one;
     if (overlaps(Y, len, X, len)) throw Error(w + ": Y aliases X");
     if (overlaps(Y, len, u, one)) throw Error(w + ": Y aliases u");
-    check_output(w, "Y", Y, len, g, mG, mask);
+    check_output(w, "Y", Y, len, g, mG, "the multipliers", mask, "the mask");
     launch_buckling_geom_apply(g, device_table(g, D_host), mG, u, mask, ncols, X, Y, s);
     VFEM_CATCH
 }
@@ -177,17 +136,15 @@ int vfem_buckling_adjoint_load(int dim, const int64_t *nelems_host, const double
     VFEM_TRY
     const std::string w = "vfem_buckling_adjoint_load";
     hipStream_t s = S(stream);
-    const ModalGrid g = buckling_setup(w, dim, nelems_host, h_host, D_host);
+    const ModalGrid g = grid_and_tensor_args(w, dim, nelems_host, h_host, D_host);
     if (!mG || !c_host || !Phi || !a) throw Error(w + ": null argument");
     check_count(w, "nmodes", nmodes, BUCKLING_MAX_MODES);
+    check_finite(w, "the coefficients are", c_host, nmodes);
     BucklingCoef c{};
-    for (int i = 0; i < nmodes; ++i) {
-        if (!std::isfinite(c_host[i])) throw Error(w + ": the coefficients are not finite");
-        c.c[i] = c_host[i];
-    }
+    for (int i = 0; i < nmodes; ++i) c.c[i] = c_host[i];
     const int64_t one = g.nnode * g.N;
     if (overlaps(a, one, Phi, nmodes * one)) throw Error(w + ": a aliases Phi");
-    check_output(w, "a", a, one, g, mG, mask);
+    check_output(w, "a", a, one, g, mG, "the multipliers", mask, "the mask");
     launch_buckling_adjoint_load(g, device_table(g, D_host), mG, mask, nmodes, c, Phi, a, s);
     VFEM_CATCH
 }
@@ -198,15 +155,15 @@ int vfem_buckling_gradient(int dim, const int64_t *nelems_host, const double *h_
     VFEM_TRY
     const std::string w = "vfem_buckling_gradient";
     hipStream_t s = S(stream);
-    const ModalGrid grid = buckling_setup(w, dim, nelems_host, h_host, D_host);
+    const ModalGrid grid = grid_and_tensor_args(w, dim, nelems_host, h_host, D_host);
     check_count(w, "nmodes", nmodes, BUCKLING_MAX_MODES);
     if (!K0_host || !cG_host || !cK_host || !dmG || !dE || !u || !v || !Phi || !g) throw Error(w + ": null argument");
     const int ke = grid.N * (1 << grid.N);
-    for (int i = 0; i < ke * ke; ++i)
-        if (!std::isfinite(K0_host[i])) throw Error(w + ": the element matrix is not finite");
+    check_finite(w, "the element matrix is", K0_host, ke * ke);
+    check_finite(w, "the coefficients are", cG_host, nmodes);
+    check_finite(w, "the coefficients are", cK_host, nmodes);
     BucklingCoef c{};
     for (int i = 0; i < nmodes; ++i) {
-        if (!std::isfinite(cG_host[i]) || !std::isfinite(cK_host[i])) throw Error(w + ": the coefficients are not finite");
         c.c[i] = cG_host[i];
         c.cK[i] = cK_host[i];
     }

@@ -1,7 +1,8 @@
-// One thread per cell of a degree-1 grid (kernels_stress.hip, kernels_modal.hip, kernels_buckling.hip): a block is 64 lanes along the last (fastest) axis
-// by 4 rows of the axis before it; in 3-D blockIdx.z walks axis 0.  A "cell" is an element (extra = 0) or a node (extra = 1) of a
-// grid with ext[d] elements per axis.  Nodes and elements are numbered with the last axis fastest; element e owns the 2^N nodes
-// (e_d + mu_d), its local node index has axis 0 as the most significant bit.
+// One thread per cell of a degree-1 grid (kernels_stress.hip, kernels_modal.hip, kernels_buckling.hip, kernels_loads.hip, and through
+// thermal_device.h kernels_thermal.hip and kernels_thermal_mg.hip): a block is 64 lanes along the last (fastest) axis by 4 rows of
+// the axis before it; in 3-D blockIdx.z walks axis 0.  A "cell" is an element (extra = 0) or a node (extra = 1) of a grid with
+// ext[d] elements per axis.  Nodes and elements are numbered with the last axis fastest; element e owns the 2^N nodes (e_d + mu_d),
+// its local node index has axis 0 as the most significant bit.
 #pragma once
 #include "vfem_internal.h"
 

@@ -2,7 +2,7 @@
 // A handle holds the hierarchy of one cell: level 0 matrix-free, Galerkin levels stored (hom_mg.h), the coarsest level as a dense
 // inverse (CoarsestSolver).  It is built once per solve; the moduli it reads at level 0 stay the caller's.
 #include "hom_mg.h"
-#include "mg_cycle.h"
+#include "mg_stored.h"
 
 #include <memory>
 
@@ -38,21 +38,10 @@ struct vfem_hom_mg {
 
 namespace {
 
-std::string dims_text(const HomGrid &g) {
-    std::string t = std::to_string(g.n[0]);
-    for (int d = 1; d < g.N; ++d) t += "x" + std::to_string(g.n[d]);
-    return t;
-}
-
 bool can_colour(const HomGrid &g) {
     for (int d = 0; d < g.N; ++d)
         if (g.n[d] % 2) return false;
     return true;
-}
-
-void check_level(const vfem_hom_mg *h, int l, const char *who, int last) {
-    if (!h) throw Error(std::string(who) + ": null handle");
-    if (l < 0 || l > last) throw Error(std::string(who) + ": level " + std::to_string(l) + " out of range");
 }
 
 // one sweep over the 2^N colours, ascending (forward) or descending
@@ -89,17 +78,6 @@ struct HomOps {
     void prolong_correction(int l) { launch_hom_mg_prolong_add(g(l), g(l + 1), x(l + 1), x(l), s); }
 };
 
-// X = V-cycle(B) from a zero initial guess: `smoothing` ascending sweeps, the coarse correction, `smoothing` descending sweeps
-void cycle_from_zero(vfem_hom_mg *h, const double *B, double *X, int smoothing, hipStream_t s) {
-    if (h->L() > 0) VFEM_HIP(hipMemsetAsync(X, 0, h->vec(0) * sizeof(double), s));
-    HomOps o{h, B, X, s};
-    mg_cycle::vcycle(o, 0, smoothing, true);
-}
-
-void check_smoothing(int smoothing, const char *who) {
-    if (smoothing < 1 || smoothing > 16) throw Error(std::string(who) + ": smoothing must be in [1, 16]");
-}
-
 }  // namespace
 
 extern "C" {
@@ -114,20 +92,15 @@ int vfem_hom_mg_create(vfem_hom_mg **out, int dim, const int64_t *nelems_host, c
     hom_setup(h->call, "vfem_hom_mg_create", dim, nelems_host, K0_host, L_host, D_host, vol, E, s);
     const HomProblem &p = h->call.p;
     const int N = p.N;
-    // the levels: coarsened while every n_d is even and at least 4 (max_coarsenings < 0: as far as that allows)
+    // the levels (max_coarsenings < 0: as far as the extents allow)
+    const auto ladder = coarsening_ladder(N, p.n, max_coarsenings);
+    const std::string sizes = ladder_text(N, ladder);
     HomGrid g = p;
-    std::string sizes = dims_text(g);
-    h->lv.emplace_back();
-    h->lv.back().g = g;
-    while (max_coarsenings < 0 || (int) h->lv.size() - 1 < max_coarsenings) {
-        bool ok = true;
-        for (int d = 0; d < N; ++d) ok = ok && g.n[d] % 2 == 0 && g.n[d] >= 4;
-        if (!ok) break;
+    for (const std::array<int, 3> &n : ladder) {
         g.pn = 1;
-        for (int d = 0; d < N; ++d) { g.n[d] /= 2; g.pn *= g.n[d]; }
+        for (int d = 0; d < N; ++d) { g.n[d] = n[d]; g.pn *= n[d]; }
         h->lv.emplace_back();
         h->lv.back().g = g;
-        sizes += ", " + dims_text(g);
     }
     const int L = h->L();
     const long long nc = (long long) g.pn * N;
@@ -196,7 +169,7 @@ int vfem_hom_mg_smooth(vfem_hom_mg *h, int l, double *X, const double *B, int fo
     VFEM_TRY
     check_level(h, l, "vfem_hom_mg_smooth", h ? h->L() : 0);
     if (!X || !B) throw Error("vfem_hom_mg_smooth: null argument");
-    if (!can_colour(h->lv[l].g)) throw Error("vfem_hom_mg_smooth: the colour sweep needs an even extent along every axis (level " + dims_text(h->lv[l].g) + ")");
+    if (!can_colour(h->lv[l].g)) throw Error("vfem_hom_mg_smooth: the colour sweep needs an even extent along every axis (level " + dims_text(h->N(), h->lv[l].g.n) + ")");
     if (l == 0 && !h->Minv0.p) {                // a one-level hierarchy never smooths: the inverses are made on demand
         h->Minv0.alloc((size_t) h->call.p.pn * h->N() * h->N());
         launch_hom_jacobi(h->call.p, h->Minv0.p, S(stream));
@@ -225,7 +198,7 @@ int vfem_hom_mg_vcycle(vfem_hom_mg *h, const double *B, double *X, int smoothing
     VFEM_TRY
     if (!h || !B || !X || B == X) throw Error("vfem_hom_mg_vcycle: B and X must be two arrays");
     check_smoothing(smoothing, "vfem_hom_mg_vcycle");
-    cycle_from_zero(h, B, X, smoothing, S(stream));
+    cycle_from_zero<HomOps>(h, B, X, smoothing, S(stream));
     VFEM_CATCH
 }
 
@@ -240,7 +213,7 @@ int vfem_hom_mg_solve_cells(vfem_hom_mg *h, double *W, double tol, int max_iter,
     // z = V-cycle(r) on all S columns at once; a one-level hierarchy is the exact inverse
     const HomPreconditioner multigrid{[&](bool first, const HomPcgVectors &v) {
         if (!first) launch_hom_mg_update(p, v.pv, v.Ap, v.x, v.r, v.st, s);
-        cycle_from_zero(h, v.r, v.z, smoothing, s);
+        cycle_from_zero<HomOps>(h, v.r, v.z, smoothing, s);
         launch_hom_mg_dots(p, v.r, v.z, v.partial, s);
     }, h->L() == 0};
     hom_pcg(p, "vfem_hom_mg_solve_cells", multigrid, W, tol, max_iter, iterations_out_host, relres_out_host, s);

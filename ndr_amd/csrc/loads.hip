@@ -1,51 +1,12 @@
 // The load-case entry points of include/vfem.h (vfem_loads_*).  Handle-free: every call takes the grid and the voxel's
 // edge lengths.  Every argument is checked before the first device call.
+#include "grid_args.h"
 #include "loads.h"
 #include "vfem_host.h"
 
-#include <cmath>
 #include <vector>
 
 using namespace vfem;
-
-namespace {
-
-ModalGrid loads_setup(const std::string &w, int dim, const int64_t *nelems, const double *h) {
-    if (dim != 2 && dim != 3) throw Error(w + ": dim must be 2 or 3");
-    if (!nelems || !h) throw Error(w + ": null argument");
-    ModalGrid g;
-    g.N = dim;
-    g.ne[2] = 1;
-    g.h[2] = 1.0;
-    g.nelem = g.nnode = 1;
-    for (int d = 0; d < dim; ++d) {
-        if (nelems[d] < 1) throw Error(w + ": every extent must be at least 1 element");
-        if (nelems[d] > (1 << 27)) throw Error(w + ": grid too large");
-        if (!(h[d] > 0.0) || !std::isfinite(h[d])) throw Error(w + ": the voxel's edge lengths must be positive");
-        g.ne[d] = (int) nelems[d];
-        g.h[d] = h[d];
-        g.nelem *= nelems[d];
-        g.nnode *= nelems[d] + 1;
-        if (g.nnode > (1LL << 31)) throw Error(w + ": grid too large (more than 2^31 nodes)");
-    }
-    return g;
-}
-
-bool overlaps_bytes(const void *a, int64_t na, const void *b, int64_t nb) {
-    const char *pa = (const char *) a, *pb = (const char *) b;
-    return pa < pb + nb && pb < pa + na;
-}
-
-bool overlaps(const double *a, int64_t na, const double *b, int64_t nb) {
-    return overlaps_bytes(a, na * (int64_t) sizeof(double), b, nb * (int64_t) sizeof(double));
-}
-
-void check_finite(const std::string &w, const char *what, const double *v, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(v[i])) throw Error(w + ": " + what + " not finite");
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -53,7 +14,7 @@ int vfem_loads_assemble(int dim, const int64_t *nelems_host, const double *h_hos
                         const double *m, const double *E, const uint8_t *mask, const double *f_in, double *f_out, void *stream) {
     VFEM_TRY
     const std::string w = "vfem_loads_assemble";
-    const ModalGrid g = loads_setup(w, dim, nelems_host, h_host);
+    const ModalGrid g = grid_args(w, dim, nelems_host, h_host, true);
     if (!f_out) throw Error(w + ": null argument");
     if (!Lb_host && !Lt_host) throw Error(w + ": null argument: neither a body-force nor an eigenstrain pattern");
     if ((Lb_host == nullptr) != (m == nullptr)) throw Error(w + ": the body-force pattern and its multipliers m go together");
@@ -83,9 +44,8 @@ int vfem_loads_gradient(int dim, const int64_t *nelems_host, const double *h_hos
     VFEM_TRY
     const std::string w = "vfem_loads_gradient";
     hipStream_t s = S(stream);
-    const ModalGrid grid = loads_setup(w, dim, nelems_host, h_host);
-    if (ncases < 1 || ncases > LOADS_MAX_CASES)
-        throw Error(w + ": ncases must be 1 to " + std::to_string(LOADS_MAX_CASES) + " (got " + std::to_string(ncases) + ")");
+    const ModalGrid grid = grid_args(w, dim, nelems_host, h_host, true);
+    check_count(w, "ncases", ncases, LOADS_MAX_CASES);
     if (!K0_host || !cK_host || !dE || !U || !g) throw Error(w + ": null argument");
     if ((Lb_host == nullptr) != (cB_host == nullptr) || (Lb_host == nullptr) != (dm == nullptr))
         throw Error(w + ": the body-force patterns, their coefficients and dm go together");

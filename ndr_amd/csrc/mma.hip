@@ -1,6 +1,7 @@
 // The MMA entry points of include/vfem.h (vfem_mma_*).  Handle-free: device pointers and a stream.  Every argument
 // is checked before the first device call.  The n-sized work is one kernel pass per evaluation of the dual (kernels_mma.hip); the
 // m x m part -- a projected Newton iteration on lambda >= 0 with a backtracking line search -- runs here on the host.
+#include "grid_args.h"
 #include "mma.h"
 #include "vfem_host.h"
 
@@ -183,8 +184,6 @@ int solve_dual(Dual &D, double tol, int max_iter, DualPoint &cur) {
                               "tolerance %.3e", max_iter, cur.residual, tol);
     throw Error(msg);
 }
-
-bool overlaps(const double *a, int64_t na, const double *b, int64_t nb) { return a < b + nb && b < a + na; }
 
 }  // namespace
 

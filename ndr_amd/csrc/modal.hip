@@ -1,40 +1,11 @@
 // The natural-frequency entry points of include/vfem.h (vfem_modal_*, vfem_block_*).  Handle-free: every grid call
 // takes the grid and the voxel's edge lengths, the block calls a length.  Every argument is checked before the first device call.
-#include "modal.h"
+#include "grid_args.h"
 #include "vfem_host.h"
-
-#include <cmath>
 
 using namespace vfem;
 
 namespace {
-
-ModalGrid modal_setup(const std::string &w, int dim, const int64_t *nelems, const double *h) {
-    if (dim != 2 && dim != 3) throw Error(w + ": dim must be 2 or 3");
-    if (!nelems || !h) throw Error(w + ": null argument");
-    ModalGrid g;
-    g.N = dim;
-    g.ne[2] = 1;
-    g.h[2] = 1.0;
-    g.nelem = g.nnode = 1;
-    for (int d = 0; d < dim; ++d) {
-        if (nelems[d] < 1) throw Error(w + ": every extent must be at least 1 element");
-        if (nelems[d] > (1 << 27)) throw Error(w + ": grid too large");
-        if (!(h[d] > 0.0) || !std::isfinite(h[d])) throw Error(w + ": the voxel's edge lengths must be positive");
-        g.ne[d] = (int) nelems[d];
-        g.h[d] = h[d];
-        g.nelem *= nelems[d];
-        g.nnode *= nelems[d] + 1;
-        if (g.nnode > (1LL << 31)) throw Error(w + ": grid too large (more than 2^31 nodes)");
-    }
-    return g;
-}
-
-void check_columns(const std::string &w, const char *what, int k, int most) {
-    if (k < 1 || k > most) throw Error(w + ": " + what + " must be 1 to " + std::to_string(most) + " (got " + std::to_string(k) + ")");
-}
-
-bool overlaps(const double *a, int64_t na, const double *b, int64_t nb) { return a < b + nb && b < a + na; }
 
 // stream-ordered scratch, as the MMA dual's is (mma.hip): taking and returning it does not synchronise the device
 struct Scratch {
@@ -54,9 +25,9 @@ int vfem_modal_mass_apply(int dim, const int64_t *nelems_host, const double *h_h
                           const double *X, double *Y, void *stream) {
     VFEM_TRY
     const std::string w = "vfem_modal_mass_apply";
-    const ModalGrid g = modal_setup(w, dim, nelems_host, h_host);
+    const ModalGrid g = grid_args(w, dim, nelems_host, h_host, true);
     if (!m || !X || !Y) throw Error(w + ": null argument");
-    check_columns(w, "ncols", ncols, BLOCK_MAX_COLS);
+    check_count(w, "ncols", ncols, BLOCK_MAX_COLS);
     const int64_t len = (int64_t) ncols * g.nnode * g.N;
     if (overlaps(Y, len, X, len)) throw Error(w + ": Y aliases X");
     launch_modal_mass_apply(g, m, mask, ncols, X, Y, S(stream));
@@ -67,9 +38,9 @@ int vfem_modal_project(int dim, const int64_t *nelems_host, const double *h_host
                        void *stream) {
     VFEM_TRY
     const std::string w = "vfem_modal_project";
-    const ModalGrid g = modal_setup(w, dim, nelems_host, h_host);
+    const ModalGrid g = grid_args(w, dim, nelems_host, h_host, true);
     if (!X) throw Error(w + ": null argument");
-    check_columns(w, "ncols", ncols, BLOCK_MAX_COLS);
+    check_count(w, "ncols", ncols, BLOCK_MAX_COLS);
     launch_modal_project(g.nnode, g.N, mask, ncols, X, S(stream));
     VFEM_CATCH
 }
@@ -79,8 +50,8 @@ int vfem_block_gram(int64_t n, int ka, const double *A, int kb, const double *B,
     const std::string w = "vfem_block_gram";
     hipStream_t s = S(stream);
     if (n < 1) throw Error(w + ": n must be at least 1");
-    check_columns(w, "ka", ka, BLOCK_MAX_COLS);
-    check_columns(w, "kb", kb, BLOCK_MAX_COLS);
+    check_count(w, "ka", ka, BLOCK_MAX_COLS);
+    check_count(w, "kb", kb, BLOCK_MAX_COLS);
     if (!A || !B) throw Error(w + ": null argument");
     if (!G && !G_host) throw Error(w + ": no output requested");
     const size_t entries = (size_t) ka * kb;
@@ -98,11 +69,10 @@ int vfem_block_combine(int64_t n, int kin, int kout, const double *A, const doub
     VFEM_TRY
     const std::string w = "vfem_block_combine";
     if (n < 1) throw Error(w + ": n must be at least 1");
-    check_columns(w, "kin", kin, BLOCK_MAX_COLS);
-    check_columns(w, "kout", kout, BLOCK_MAX_COLS);
+    check_count(w, "kin", kin, BLOCK_MAX_COLS);
+    check_count(w, "kout", kout, BLOCK_MAX_COLS);
     if (!A || !C_host || !B) throw Error(w + ": null argument");
-    for (int i = 0; i < kin * kout; ++i)
-        if (!std::isfinite(C_host[i])) throw Error(w + ": the coefficients are not finite");
+    check_finite(w, "the coefficients are", C_host, kin * kout);
     if (overlaps(B, n * kout, A, n * kin)) throw Error(w + ": B aliases A");
     launch_block_combine(n, kin, kout, A, C_host, B, S(stream));
     VFEM_CATCH
@@ -114,15 +84,15 @@ int vfem_modal_gradient(int dim, const int64_t *nelems_host, const double *h_hos
     VFEM_TRY
     const std::string w = "vfem_modal_gradient";
     hipStream_t s = S(stream);
-    const ModalGrid grid = modal_setup(w, dim, nelems_host, h_host);
-    check_columns(w, "nmodes", nmodes, MODAL_MAX_MODES);
+    const ModalGrid grid = grid_args(w, dim, nelems_host, h_host, true);
+    check_count(w, "nmodes", nmodes, MODAL_MAX_MODES);
     if (!K0_host || !cK_host || !cM_host || !dE || !dm || !Phi || !g) throw Error(w + ": null argument");
     const int ke = grid.N * (1 << grid.N);
-    for (int i = 0; i < ke * ke; ++i)
-        if (!std::isfinite(K0_host[i])) throw Error(w + ": the element matrix is not finite");
+    check_finite(w, "the element matrix is", K0_host, ke * ke);
+    check_finite(w, "the coefficients are", cK_host, nmodes);
+    check_finite(w, "the coefficients are", cM_host, nmodes);
     ModalCoef c{};
     for (int i = 0; i < nmodes; ++i) {
-        if (!std::isfinite(cK_host[i]) || !std::isfinite(cM_host[i])) throw Error(w + ": the coefficients are not finite");
         c.cK[i] = cK_host[i];
         c.cM[i] = cM_host[i];
     }

@@ -1,39 +1,26 @@
 // The element-stress entry points of include/vfem.h (vfem_stress_*).  Handle-free: every call takes the grid, the voxel's
 // edge lengths and the flattened tensor.  Every argument is checked before the first device call.
+#include "grid_args.h"
 #include "stress.h"
 #include "vfem_host.h"
-
-#include <cmath>
 
 using namespace vfem;
 
 namespace {
 
 StressProblem stress_setup(const char *who, int dim, const int64_t *nelems, const double *h, const double *D) {
-    const std::string w(who);
-    if (dim != 2 && dim != 3) throw Error(w + ": dim must be 2 or 3");
-    if (!nelems || !h || !D) throw Error(w + ": null argument");
+    const ModalGrid g = grid_and_tensor_args(who, dim, nelems, h, D);
     StressProblem p;
     p.N = dim;
     p.S = dim == 2 ? 3 : 6;
-    p.ne[2] = 1;
-    p.gs[2] = 0.0;
-    p.nelem = p.nnode = 1;
-    for (int d = 0; d < dim; ++d) {
-        if (nelems[d] < 1) throw Error(w + ": every extent must be at least 1 element");
-        if (nelems[d] > (1 << 27)) throw Error(w + ": grid too large");
-        if (!(h[d] > 0.0) || !std::isfinite(h[d])) throw Error(w + ": the voxel's edge lengths must be positive");
-        p.ne[d] = (int) nelems[d];
-        p.gs[d] = 1.0 / (h[d] * (double) (1 << (dim - 1)));
-        p.nelem *= nelems[d];
-        p.nnode *= nelems[d] + 1;
-        if (p.nnode > (1LL << 31)) throw Error(w + ": grid too large (more than 2^31 nodes)");
+    for (int d = 0; d < 3; ++d) {
+        p.ne[d] = g.ne[d];
+        p.gs[d] = d < dim ? 1.0 / (g.h[d] * (double) (1 << (dim - 1))) : 0.0;
     }
+    p.nelem = g.nelem;
+    p.nnode = g.nnode;
     for (int q = 0; q < p.S; ++q)
-        for (int r = 0; r < p.S; ++r) {
-            if (!std::isfinite(D[q * p.S + r])) throw Error(w + ": the tensor is not finite");
-            p.Dm[q * p.S + r] = D[q * p.S + r] * (r < dim ? 1.0 : 2.0);
-        }
+        for (int r = 0; r < p.S; ++r) p.Dm[q * p.S + r] = D[q * p.S + r] * (r < dim ? 1.0 : 2.0);
     for (int i = p.S * p.S; i < 36; ++i) p.Dm[i] = 0.0;
     return p;
 }
@@ -100,8 +87,7 @@ int vfem_stress_pnorm_gradient(int dim, const int64_t *nelems_host, const double
     check_exponent("vfem_stress_pnorm_gradient", P);
     check_measure("vfem_stress_pnorm_gradient", J);
     const int ke = p.N * (1 << p.N);
-    for (int i = 0; i < ke * ke; ++i)
-        if (!std::isfinite(K0_host[i])) throw Error("vfem_stress_pnorm_gradient: the element matrix is not finite");
+    check_finite("vfem_stress_pnorm_gradient", "the element matrix is", K0_host, ke * ke);
     if (J == 0.0) {
         VFEM_HIP(hipMemsetAsync(g, 0, (size_t) p.nelem * sizeof(double), s));
     } else {

@@ -54,9 +54,8 @@ void launch_thermal_scale(long long n, const double *dinv, const double *r, doub
 // on both stages make the step and the direction update neutral (alpha = 0, beta = 0), so the loop idles until the host looks.
 void launch_thermal_pcg_guard(double *sc, int stage, int iteration, hipStream_t s);
 
-// Host code of thermal.hip that thermal_mg.hip uses too.  The argument checks every vfem_thermal_* call starts with (w: the entry
-// point's name for the message):
-ModalGrid thermal_grid(const std::string &w, int dim, const int64_t *nelems_host);
+// Host code of thermal.hip that thermal_mg.hip uses too.  The element matrix of an entry point, after its grid (grid_args.h; w: the
+// entry point's name for the message): there and finite
 ThermalMatrix thermal_element_matrix(const std::string &w, int dim, const double *Kc0_host);
 // The PCG loop of vfem_thermal_pcg and vfem_thermal_mg_pcg on A x = b from the x given: z = M^-1 r is the caller's (launched on s);
 // the host reads the scalars before the first iteration and then every look_every iterations, stops when |r| / |b| <= tol, and

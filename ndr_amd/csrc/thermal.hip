@@ -1,10 +1,10 @@
 // The heat-conduction entry points of include/vfem.h (vfem_thermal_*).  Handle-free: every call takes the grid, and
 // the element matrix or the voxel's edge lengths where its kernel needs them.  Every argument is checked before the first device
 // call.
+#include "grid_args.h"
 #include "thermal.h"
 #include "vfem_host.h"
 
-#include <cmath>
 #include <cstdio>
 
 using namespace vfem;
@@ -13,67 +13,24 @@ namespace {
 
 constexpr int THERMAL_PCG_CHECK = 8;        // the host looks at the residual once every so many iterations, as the cell problems do
 
-ModalGrid thermal_setup(const std::string &w, int dim, const int64_t *nelems, const double *h) {
-    if (dim != 2 && dim != 3) throw Error(w + ": dim must be 2 or 3");
-    if (!nelems) throw Error(w + ": null argument");
-    ModalGrid g;
-    g.N = dim;
-    g.ne[2] = 1;
-    g.h[0] = g.h[1] = g.h[2] = 1.0;
-    g.nelem = g.nnode = 1;
-    for (int d = 0; d < dim; ++d) {
-        if (nelems[d] < 1) throw Error(w + ": every extent must be at least 1 element");
-        if (nelems[d] > (1 << 27)) throw Error(w + ": grid too large");
-        if (h) {
-            if (!(h[d] > 0.0) || !std::isfinite(h[d])) throw Error(w + ": the voxel's edge lengths must be positive");
-            g.h[d] = h[d];
-        }
-        g.ne[d] = (int) nelems[d];
-        g.nelem *= nelems[d];
-        g.nnode *= nelems[d] + 1;
-        if (g.nnode > (1LL << 31)) throw Error(w + ": grid too large (more than 2^31 nodes)");
-    }
-    return g;
-}
-
-ThermalMatrix thermal_matrix(const std::string &w, int dim, const double *Kc0) {
-    if (!Kc0) throw Error(w + ": null argument");
-    ThermalMatrix K{};
-    const int npe = 1 << dim;
-    for (int i = 0; i < npe * npe; ++i) {
-        if (!std::isfinite(Kc0[i])) throw Error(w + ": the element matrix is not finite");
-        K.k[i] = Kc0[i];
-    }
-    return K;
-}
-
-void check_columns(const std::string &w, int k) {
-    if (k < 1 || k > THERMAL_MAX_COLS)
-        throw Error(w + ": ncols must be 1 to " + std::to_string(THERMAL_MAX_COLS) + " (got " + std::to_string(k) + ")");
-}
-
-bool overlaps_bytes(const void *a, int64_t na, const void *b, int64_t nb) {
-    const char *pa = (const char *) a, *pb = (const char *) b;
-    return pa < pb + nb && pb < pa + na;
-}
-
-bool overlaps(const double *a, int64_t na, const double *b, int64_t nb) {
-    return overlaps_bytes(a, na * (int64_t) sizeof(double), b, nb * (int64_t) sizeof(double));
-}
-
-// an output of `len` doubles against the element multipliers and the fixed-node bytes
-void check_output(const std::string &w, const char *name, const ModalGrid &g, const double *out, int64_t len, const double *kappa,
-                  const uint8_t *fixed) {
-    if (kappa && overlaps(out, len, kappa, g.nelem)) throw Error(w + ": " + name + " aliases the element multipliers");
-    if (fixed && overlaps_bytes(out, len * (int64_t) sizeof(double), fixed, g.nnode)) throw Error(w + ": " + name + " aliases the fixed-node mask");
+// an output of `len` doubles against the element multipliers and the fixed-node bytes (either may be null)
+void check_thermal_output(const std::string &w, const char *name, const ModalGrid &g, const double *out, int64_t len, const double *kappa,
+                          const uint8_t *fixed) {
+    check_output(w, name, out, len, g, kappa, "the element multipliers", fixed, "the fixed-node mask");
 }
 
 }  // namespace
 
 namespace vfem {
 
-ModalGrid thermal_grid(const std::string &w, int dim, const int64_t *nelems) { return thermal_setup(w, dim, nelems, nullptr); }
-ThermalMatrix thermal_element_matrix(const std::string &w, int dim, const double *Kc0) { return thermal_matrix(w, dim, Kc0); }
+ThermalMatrix thermal_element_matrix(const std::string &w, int dim, const double *Kc0) {
+    if (!Kc0) throw Error(w + ": null argument");
+    const int npe = 1 << dim;
+    check_finite(w, "the element matrix is", Kc0, npe * npe);
+    ThermalMatrix K{};
+    for (int i = 0; i < npe * npe; ++i) K.k[i] = Kc0[i];
+    return K;
+}
 
 void thermal_pcg(const std::string &w, const ModalGrid &g, const ThermalMatrix &K, const double *kappa, const uint8_t *fixed,
                  const double *b, double *x, double tol, int max_iter, int look_every, const ThermalPreconditioner &precondition,
@@ -149,13 +106,13 @@ int vfem_thermal_apply(int dim, const int64_t *nelems_host, const double *Kc0_ho
                        int ncols, const double *X, double *Y, void *stream) {
     VFEM_TRY
     const std::string w = "vfem_thermal_apply";
-    const ModalGrid g = thermal_setup(w, dim, nelems_host, nullptr);
-    const ThermalMatrix K = thermal_matrix(w, dim, Kc0_host);
+    const ModalGrid g = grid_args(w, dim, nelems_host, nullptr, false);
+    const ThermalMatrix K = thermal_element_matrix(w, dim, Kc0_host);
     if (!kappa || !X || !Y) throw Error(w + ": null argument");
-    check_columns(w, ncols);
+    check_count(w, "ncols", ncols, THERMAL_MAX_COLS);
     const int64_t len = (int64_t) ncols * g.nnode;
     if (overlaps(Y, len, X, len)) throw Error(w + ": Y aliases X");
-    check_output(w, "Y", g, Y, len, kappa, fixed);
+    check_thermal_output(w, "Y", g, Y, len, kappa, fixed);
     launch_thermal_apply(g, K, kappa, fixed, ncols, X, nullptr, Y, S(stream));
     VFEM_CATCH
 }
@@ -164,10 +121,10 @@ int vfem_thermal_diagonal(int dim, const int64_t *nelems_host, const double *Kc0
                           double *diag, void *stream) {
     VFEM_TRY
     const std::string w = "vfem_thermal_diagonal";
-    const ModalGrid g = thermal_setup(w, dim, nelems_host, nullptr);
-    const ThermalMatrix K = thermal_matrix(w, dim, Kc0_host);
+    const ModalGrid g = grid_args(w, dim, nelems_host, nullptr, false);
+    const ThermalMatrix K = thermal_element_matrix(w, dim, Kc0_host);
     if (!kappa || !diag) throw Error(w + ": null argument");
-    check_output(w, "diag", g, diag, g.nnode, kappa, fixed);
+    check_thermal_output(w, "diag", g, diag, g.nnode, kappa, fixed);
     launch_thermal_diagonal(g, K, kappa, fixed, 0, diag, S(stream));
     VFEM_CATCH
 }
@@ -176,12 +133,12 @@ int vfem_thermal_source(int dim, const int64_t *nelems_host, const double *h_hos
                         const double *f_in, double *f_out, void *stream) {
     VFEM_TRY
     const std::string w = "vfem_thermal_source";
-    if (!h_host) throw Error(w + ": null argument");
-    const ModalGrid g = thermal_setup(w, dim, nelems_host, h_host);
+    if (!h_host) throw Error(w + ": null argument");            // (this call refuses missing edge lengths before a bad dim)
+    const ModalGrid g = grid_args(w, dim, nelems_host, h_host, true);
     if (!f_out) throw Error(w + ": null argument");
     if (!q && !f_in) throw Error(w + ": null argument: neither a volumetric nor a nodal source");
     if (f_in && f_in != f_out && overlaps(f_out, g.nnode, f_in, g.nnode)) throw Error(w + ": f_out overlaps f_in without being f_in");
-    check_output(w, "f_out", g, f_out, g.nnode, q, fixed);
+    check_thermal_output(w, "f_out", g, f_out, g.nnode, q, fixed);
     launch_thermal_source(g, q, fixed, f_in, f_out, S(stream));
     VFEM_CATCH
 }
@@ -190,12 +147,12 @@ int vfem_thermal_band_assemble(int dim, const int64_t *nelems_host, const double
                                double *band, void *stream) {
     VFEM_TRY
     const std::string w = "vfem_thermal_band_assemble";
-    const ModalGrid g = thermal_setup(w, dim, nelems_host, nullptr);
-    const ThermalMatrix K = thermal_matrix(w, dim, Kc0_host);
+    const ModalGrid g = grid_args(w, dim, nelems_host, nullptr, false);
+    const ThermalMatrix K = thermal_element_matrix(w, dim, Kc0_host);
     if (!kappa || !band) throw Error(w + ": null argument");
     long long n, hw;
     thermal_band_geometry(g, n, hw);
-    check_output(w, "band", g, band, band_spd_doubles(n, hw), kappa, fixed);
+    check_thermal_output(w, "band", g, band, band_spd_doubles(n, hw), kappa, fixed);
     launch_thermal_band_assemble(g, K, kappa, fixed, band, S(stream));
     VFEM_CATCH
 }
@@ -206,13 +163,13 @@ int vfem_thermal_pcg(int dim, const int64_t *nelems_host, const double *Kc0_host
     VFEM_TRY
     const std::string w = "vfem_thermal_pcg";
     hipStream_t s = S(stream);
-    const ModalGrid g = thermal_setup(w, dim, nelems_host, nullptr);
-    const ThermalMatrix K = thermal_matrix(w, dim, Kc0_host);
+    const ModalGrid g = grid_args(w, dim, nelems_host, nullptr, false);
+    const ThermalMatrix K = thermal_element_matrix(w, dim, Kc0_host);
     if (!kappa || !b || !x || !iterations_out_host || !relres_out_host) throw Error(w + ": null argument");
     if (!(tol > 0.0) || !std::isfinite(tol) || max_iter < 1) throw Error(w + ": tol must be positive and max_iter at least 1");
     const long long n = g.nnode;
     if (overlaps(x, n, b, n)) throw Error(w + ": x aliases b");
-    check_output(w, "x", g, x, n, kappa, fixed);
+    check_thermal_output(w, "x", g, x, n, kappa, fixed);
     DevBuf<double> dinv;
     dinv.alloc((size_t) n);
     launch_thermal_diagonal(g, K, kappa, fixed, 1, dinv.p, s);
@@ -225,15 +182,13 @@ int vfem_thermal_gradient(int dim, const int64_t *nelems_host, int ncols, const 
                           const double *dkappa, const double *A, const double *B, double *g, void *stream) {
     VFEM_TRY
     const std::string w = "vfem_thermal_gradient";
-    const ModalGrid grid = thermal_setup(w, dim, nelems_host, nullptr);
-    check_columns(w, ncols);
-    const ThermalMatrix K = thermal_matrix(w, dim, Kc0_host);
+    const ModalGrid grid = grid_args(w, dim, nelems_host, nullptr, false);
+    check_count(w, "ncols", ncols, THERMAL_MAX_COLS);
+    const ThermalMatrix K = thermal_element_matrix(w, dim, Kc0_host);
     if (!c_host || !dkappa || !A || !B || !g) throw Error(w + ": null argument");
+    check_finite(w, "the coefficients are", c_host, ncols);
     ThermalCoef c{};
-    for (int i = 0; i < ncols; ++i) {
-        if (!std::isfinite(c_host[i])) throw Error(w + ": the coefficients are not finite");
-        c.c[i] = c_host[i];
-    }
+    for (int i = 0; i < ncols; ++i) c.c[i] = c_host[i];
     const int64_t len = (int64_t) ncols * grid.nnode;
     if (overlaps(g, grid.nelem, A, len) || overlaps(g, grid.nelem, B, len) || overlaps(g, grid.nelem, dkappa, grid.nelem))
         throw Error(w + ": g aliases an input");
@@ -245,14 +200,12 @@ int vfem_thermal_flux(int dim, const int64_t *nelems_host, const double *h_host,
                       const double *T, double *flux, void *stream) {
     VFEM_TRY
     const std::string w = "vfem_thermal_flux";
-    if (!h_host) throw Error(w + ": null argument");
-    const ModalGrid g = thermal_setup(w, dim, nelems_host, h_host);
+    if (!h_host) throw Error(w + ": null argument");            // (this call refuses missing edge lengths before a bad dim)
+    const ModalGrid g = grid_args(w, dim, nelems_host, h_host, true);
     if (!k_host || !kappa || !T || !flux) throw Error(w + ": null argument");
+    check_finite(w, "the conductivity tensor is", k_host, dim * dim);
     ThermalTensor k{};
-    for (int i = 0; i < dim * dim; ++i) {
-        if (!std::isfinite(k_host[i])) throw Error(w + ": the conductivity tensor is not finite");
-        k.k[i] = k_host[i];
-    }
+    for (int i = 0; i < dim * dim; ++i) k.k[i] = k_host[i];
     if (overlaps(flux, g.nelem * dim, T, g.nnode) || overlaps(flux, g.nelem * dim, kappa, g.nelem)) throw Error(w + ": flux aliases an input");
     launch_thermal_flux(g, k, kappa, T, flux, S(stream));
     VFEM_CATCH

@@ -3,9 +3,9 @@
 // levels stored (thermal_mg.h), the coarsest level as a dense inverse (CoarsestSolver).  The V-cycle is mg_cycle::vcycle, the colour
 // order for_each_gs_color, the PCG loop thermal_pcg (thermal.hip) with z = V-cycle(r).  Every argument is checked before the first
 // device call.
+#include "grid_args.h"
+#include "mg_stored.h"
 #include "thermal_mg.h"
-
-#include "mg_cycle.h"
 
 #include <memory>
 
@@ -27,6 +27,7 @@ struct vfem_thermal_mg {
     CoarsestSolver coarsest;
     int N() const { return lv[0].g.N; }
     int L() const { return (int) lv.size() - 1; }
+    size_t vec(int l) const { return (size_t) lv[l].g.nnode; }
     ThermalLevelOp op(int l) const { return l == 0 ? ThermalLevelOp{nullptr, kappa, &K} : ThermalLevelOp{lv[l].A.p, nullptr, nullptr}; }
     long long bytes() const {
         size_t d = 0, m = 0;
@@ -39,23 +40,6 @@ struct vfem_thermal_mg {
 };
 
 namespace {
-
-std::string dims_text(const ModalGrid &g) {
-    std::string t = std::to_string(g.ne[0]);
-    for (int d = 1; d < g.N; ++d) t += "x" + std::to_string(g.ne[d]);
-    return t;
-}
-
-void check_level(const vfem_thermal_mg *h, int l, const char *who, int last) {
-    if (!h) throw Error(std::string(who) + ": null handle");
-    if (l < 0 || l > last) throw Error(std::string(who) + ": level " + std::to_string(l) + " out of range");
-}
-
-void check_smoothing(int smoothing, const char *who) {
-    if (smoothing < 1 || smoothing > 16) throw Error(std::string(who) + ": smoothing must be in [1, 16]");
-}
-
-bool overlaps(const double *a, long long na, const double *b, long long nb) { return a < b + nb && b < a + na; }
 
 // a one-level hierarchy never smooths: its inverted diagonal is made on demand
 void need_dinv0(vfem_thermal_mg *h, hipStream_t s) {
@@ -103,19 +87,12 @@ struct ThermalOps {
     void restrict_residual(int l) {
         launch_thermal_mg_restrict(h->lv[l].g, h->lv[l + 1].g, h->lv[l].fixed.p, h->lv[l + 1].fixed.p, r(l), h->lv[l + 1].b.p, s);
         // a smoothed level starts from zero; the coarsest x is overwritten by the dense product
-        if (l + 1 < h->L()) VFEM_HIP(hipMemsetAsync(x(l + 1), 0, (size_t) h->lv[l + 1].g.nnode * sizeof(double), s));
+        if (l + 1 < h->L()) VFEM_HIP(hipMemsetAsync(x(l + 1), 0, h->vec(l + 1) * sizeof(double), s));
     }
     void prolong_correction(int l) {
         launch_thermal_mg_prolong_add(h->lv[l].g, h->lv[l + 1].g, h->lv[l].fixed.p, h->lv[l + 1].fixed.p, x(l + 1), x(l), s);
     }
 };
-
-// X = V-cycle(B) from a zero initial guess: `smoothing` ascending sweeps, the coarse correction, `smoothing` descending sweeps
-void cycle_from_zero(vfem_thermal_mg *h, const double *B, double *X, int smoothing, hipStream_t s) {
-    if (h->L() > 0) VFEM_HIP(hipMemsetAsync(X, 0, (size_t) h->lv[0].g.nnode * sizeof(double), s));
-    ThermalOps o{h, B, X, s};
-    mg_cycle::vcycle(o, 0, smoothing, true);
-}
 
 }  // namespace
 
@@ -128,31 +105,26 @@ int vfem_thermal_mg_create(vfem_thermal_mg **out, int dim, const int64_t *nelems
     if (!out) throw Error(w + ": null argument");
     *out = nullptr;
     hipStream_t s = S(stream);
-    ModalGrid g = thermal_grid(w, dim, nelems_host);
+    ModalGrid g = grid_args(w, dim, nelems_host, nullptr, false);
     std::unique_ptr<vfem_thermal_mg> h(new vfem_thermal_mg);
     h->K = thermal_element_matrix(w, dim, Kc0_host);
     if (!kappa) throw Error(w + ": null argument");
     h->kappa = kappa;
     h->fixed_in = fixed;
     const int N = g.N;
-    // the levels: coarsened while every extent is even and at least 4 (max_coarsenings < 0: as far as that allows)
-    std::string sizes = dims_text(g);
-    h->lv.emplace_back();
-    h->lv.back().g = g;
-    while (max_coarsenings < 0 || (int) h->lv.size() - 1 < max_coarsenings) {
-        bool ok = true;
-        for (int d = 0; d < N; ++d) ok = ok && g.ne[d] % 2 == 0 && g.ne[d] >= 4;
-        if (!ok) break;
+    // the levels (max_coarsenings < 0: as far as the extents allow); a coarser voxel has twice the edge lengths
+    const auto ladder = coarsening_ladder(N, g.ne, max_coarsenings);
+    const std::string sizes = ladder_text(N, ladder);
+    for (size_t l = 0; l < ladder.size(); ++l) {
         g.nelem = g.nnode = 1;
         for (int d = 0; d < N; ++d) {
-            g.ne[d] /= 2;
-            g.h[d] *= 2.0;
+            g.ne[d] = ladder[l][d];
+            if (l > 0) g.h[d] *= 2.0;
             g.nelem *= g.ne[d];
             g.nnode *= g.ne[d] + 1;
         }
         h->lv.emplace_back();
         h->lv.back().g = g;
-        sizes += ", " + dims_text(g);
     }
     const int L = h->L();
     const long long nc = g.nnode;
@@ -276,7 +248,7 @@ int vfem_thermal_mg_vcycle(vfem_thermal_mg *h, const double *B, double *X, int s
     check_smoothing(smoothing, "vfem_thermal_mg_vcycle");
     if (!h) throw Error("vfem_thermal_mg_vcycle: null handle");
     if (overlaps(X, h->lv[0].g.nnode, B, h->lv[0].g.nnode)) throw Error("vfem_thermal_mg_vcycle: X aliases B");
-    cycle_from_zero(h, B, X, smoothing, S(stream));
+    cycle_from_zero<ThermalOps>(h, B, X, smoothing, S(stream));
     VFEM_CATCH
 }
 
@@ -292,7 +264,7 @@ int vfem_thermal_mg_pcg(vfem_thermal_mg *h, const double *b, double *x, double t
     const ModalGrid &g = h->lv[0].g;
     if (overlaps(x, g.nnode, b, g.nnode)) throw Error(w + ": x aliases b");
     // z = V-cycle(r); the host looks after every iteration, so the count is exact: a look costs little beside a cycle
-    const ThermalPreconditioner multigrid = [&](const double *r, double *z) { cycle_from_zero(h, r, z, smoothing, s); };
+    const ThermalPreconditioner multigrid = [&](const double *r, double *z) { cycle_from_zero<ThermalOps>(h, r, z, smoothing, s); };
     thermal_pcg(w, g, h->K, h->kappa, h->lv[0].fixed.p, b, x, tol, max_iter, 1, multigrid, iterations_out_host, relres_out_host, s);
     VFEM_CATCH
 }

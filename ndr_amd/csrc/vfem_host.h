@@ -1,5 +1,6 @@
-// Host-only declarations shared by the translation units of the C boundary (capi, sim, mg, mg_slab, design, mlp and the host
-// half of generic): the try / catch frame of an entry point, the section timers, and the few functions that cross files.
+// Host-only declarations shared by the translation units of the C boundary (capi, sim, mg, mg_slab, design, mlp, coarsest,
+// plane_spd, hom, hom_mg, stress, mma, modal, buckling, loads, thermal, thermal_mg and the host half of generic): the try / catch
+// frame of an entry point, the section timers, and the few functions that cross files.
 #pragma once
 #include "vfem_internal.h"
 

@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from . import materials as _materials
+from ._grid import Grid, _dp, simp_multipliers
 from .pyVoxelFEM import _dev, _ptr, _stream, _stress_load, _to_np
 
 __all__ = ["solveCellProblems", "solveCellProblems_device", "homogenizedElasticityTensor", "homogenizedElasticityTensor_device",
@@ -36,25 +37,16 @@ last_relative_residuals = []     # |r| / |b| of each strain case at its end
 last_levels = []                 # per-level cell sizes of the last multigrid solve: [[n_0, ..], [n_0 / 2, ..], ..]
 
 
-def _dp(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-
-
-class _Cell:
+class _Cell(Grid):
     """what every ``vfem_hom_*`` call starts with, taken from a simulator: the grid, K0, L, D, the voxel volume, the moduli"""
 
     def __init__(self, sim):
-        N = getattr(sim, "N", None)
-        if N not in (2, 3) or getattr(sim, "P", None) != 1:
-            raise RuntimeError("periodic homogenisation needs a degree-1 simulator (TensorProductSimulator1_1 or 1_1_1)")
-        if sim._num_stored_elements() != sim.numElements():
-            raise RuntimeError("periodic homogenisation needs a whole cell: this simulator stores slab padding layers")
-        ne = [int(n) for n in sim.NbElementsPerDimension()]
+        super().__init__(sim, "periodic homogenisation needs", whole="cell")
+        N, ne, h = self.N, self.ne, self.h
         if min(ne) < 2:
             raise RuntimeError("periodic homogenisation needs at least 2 elements along every axis (got %s)" % "x".join(map(str, ne)))
-        self.N, self.S, self.ne = N, 3 if N == 2 else 6, ne
+        self.S = 3 if N == 2 else 6
         self.pn = int(np.prod(ne))
-        h = (sim._bbmax - sim._bbmin) / np.asarray(ne, dtype=np.float64)
         self.vol = float(np.prod(h))
         self.cell_volume = self.vol * self.pn
         tensor = sim.ETensor
@@ -68,15 +60,10 @@ class _Cell:
             eps[i, j] = eps[j, i] = 1.0 if i == j else 0.5
             L[:, q] = _stress_load(tensor.doubleContract(eps), h, 1, one).numpy().reshape(-1)
         self.L = np.ascontiguousarray(L)
-        rho = sim.getDensities_device()[:self.pn]
-        E0, Emin, gamma = float(sim.E_0), float(sim.E_min), float(sim.gamma)
-        self.E = (Emin + rho ** gamma * (E0 - Emin)).contiguous()
-        self.dE = (gamma * rho ** (gamma - 1.0) * (E0 - Emin)).contiguous()
-        self._nelems = np.asarray(ne, dtype=np.int64)
+        self.E, self.dE = simp_multipliers(sim, sim.getDensities_device()[:self.pn])
 
     def head(self):
-        return (self.N, self._nelems.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _dp(self.K0), _dp(self.L), _dp(self.D), self.vol,
-                _ptr(self.E))
+        return super().head(_dp(self.K0), _dp(self.L), _dp(self.D), self.vol, _ptr(self.E))
 
     # ---- full node grid <-> periodic node grid ----
     def to_full(self, Wp):

@@ -28,22 +28,17 @@ With fixed loads only the gradient is nowhere positive and ``OCOptimizer`` works
 signs (material added above a span weighs on it; on a 16 x 6 arch under its own weight tests/test_loadcases_cpu.py pins the
 counts): use ``ndr_amd.mma.MMAOptimizer`` or ``aggregateCompliance`` with a torch optimiser.
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib, modal
+from ._grid import ObjectiveFunction, _dp, simp_multipliers
 from .pyVoxelFEM import _dev, _matched_regions, _ptr, _stream, _to_dev, _to_np, _write_force_region, _MultigridSolver
 
 __all__ = ["LoadCase", "thermalStrain", "loadsFromFile", "assembleLoad", "assembleLoad_device", "LoadCaseComplianceObjective",
            "AggregateComplianceFunction", "aggregateCompliance", "MAX_CASES"]
 
 MAX_CASES = 8
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
 def _opt(t):
@@ -103,16 +98,11 @@ class _Grid(modal._Grid):
     kernels do not take, and the element patterns and multipliers of a case"""
 
     def __init__(self, sim):
-        N = getattr(sim, "N", None)
-        if N not in (2, 3) or getattr(sim, "P", None) != 1:
-            raise RuntimeError("load cases need a degree-1 simulator (TensorProductSimulator1_1 or 1_1_1)")
-        if sim._num_stored_elements() != sim.numElements():
-            raise RuntimeError("load cases need a whole grid: this simulator stores slab padding layers")
+        super().__init__(sim, "load cases need")
         if np.any(sim._dvals[sim._mask] != 0):
             raise RuntimeError("load cases: nonzero Dirichlet values are not supported (the loads are those of the clamped body)")
-        super().__init__(sim)
         self.vol = float(np.prod(self.h))
-        self.ke = N * 2 ** N
+        self.ke = self.N * 2 ** self.N
 
     def patterns(self, case):
         """(Lb, Lt) of a case: numpy [ke] each, or None"""
@@ -147,9 +137,7 @@ class _Grid(modal._Grid):
         return _to_dev(case.loads, (self.nnode, self.N)).clone()
 
     def stiffness_multipliers(self, rho):
-        sim = self.sim
-        gamma, E0, Emin = float(sim.gamma), float(sim.E_0), float(sim.E_min)
-        return (Emin + rho ** gamma * (E0 - Emin)).contiguous(), (gamma * rho ** (gamma - 1.0) * (E0 - Emin)).contiguous()
+        return simp_multipliers(self.sim, rho)
 
     def assemble(self, F, Lb, Lt, m, E):
         """P (F + sum_e m Lb + sum_e E Lt) as a new device tensor; F may be None"""
@@ -432,26 +420,11 @@ class LoadCaseComplianceObjective:
         return _to_np(self.gradient_device())
 
 
-class AggregateComplianceFunction(torch.autograd.Function):
+class AggregateComplianceFunction(ObjectiveFunction):
     """J of the predicted densities as an autograd node, the counterpart of ``modal.MeanEigenvalueFunction``: forward sets the
     densities and solves every case; backward is ``gradient_device()`` weighted by the incoming gradient."""
 
-    @staticmethod
-    def forward(ctx, densities, objective):
-        objective.updateCache(densities.detach().reshape(-1))
-        ctx.objective, ctx.u, ctx.dtype, ctx.shape = objective, objective._u, densities.dtype, densities.shape
-        return torch.tensor(objective.evaluate(), dtype=torch.float64, device=densities.device)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        obj = ctx.objective
-        if obj._state is None or obj._u is not ctx.u:
-            raise RuntimeError("aggregateCompliance: the objective was updated between forward and backward")
-        w = float(grad_output.detach().cpu())
-        g = obj.gradient_device()
-        if w != 1.0:
-            g = w * g
-        return g.to(ctx.dtype).reshape(ctx.shape), None
+    NAME = "aggregateCompliance"
 
 
 def aggregateCompliance(densities, objective):

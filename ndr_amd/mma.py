@@ -19,15 +19,12 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._grid import _dp
 from .pyVoxelFEM import _dev, _ptr, _stream, _to_dev, _to_np
 
 __all__ = ["MMAOptimizer", "ObjectiveConstraint", "VolumeObjective", "MAX_CONSTRAINTS"]
 
 MAX_CONSTRAINTS = 8
-
-
-def _dp(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
 class VolumeObjective:

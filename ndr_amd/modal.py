@@ -13,12 +13,11 @@ in ``libvfem.so`` (``vfem_modal_*``, ``vfem_block_*``, include/vfem.h); DESIGN 3
     M(rho) = sum_e m(rho_e) M0,  M0 = the consistent mass matrix of a unit-density voxel,  m(rho) = massDensity rho^massExponent
     J = sum_{i <= k} 1 / lambda_i,   dJ/drho_e = -sum_i lambda_i^-2 (dE_e phi_ie^T K0 phi_ie - lambda_i dm_e phi_ie^T M0 phi_ie)
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
+from ._grid import Grid, ObjectiveFunction, _dp, simp_multipliers
 from .pyVoxelFEM import _dev, _ptr, _stream, _to_dev, _to_np, _MultigridSolver
 
 __all__ = ["massMultipliers", "applyM", "applyM_device", "eigenmodes", "MeanEigenvalueObjective", "MeanEigenvalueFunction",
@@ -28,33 +27,15 @@ MAX_MODES = 8           # modes asked for
 MAX_BLOCK = 8           # modes plus guard columns: the basis [W, P, X] has three blocks and a Gram matrix at most 24 columns
 
 
-def _dp(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
-
-
-class _Grid:
+class _Grid(Grid):
     """what every ``vfem_modal_*`` grid call starts with, taken from a simulator: the grid and the voxel's edge lengths"""
 
-    def __init__(self, sim):
-        N = getattr(sim, "N", None)
-        if N not in (2, 3) or getattr(sim, "P", None) != 1:
-            raise RuntimeError("natural frequencies need a degree-1 simulator (TensorProductSimulator1_1 or 1_1_1)")
-        if sim._num_stored_elements() != sim.numElements():
-            raise RuntimeError("natural frequencies need a whole grid: this simulator stores slab padding layers")
-        self.sim, self.N = sim, N
-        self.ne = [int(n) for n in sim.NbElementsPerDimension()]
-        self.nelem, self.nnode = sim.numElements(), sim.numNodes()
-        self.n = self.nnode * N
-        self.h = np.ascontiguousarray((sim._bbmax - sim._bbmin) / np.asarray(self.ne, dtype=np.float64))
-        self._nelems = np.asarray(self.ne, dtype=np.int64)
-        bits = np.zeros(self.nnode, dtype=np.uint8)
-        for c in range(N):
-            bits |= sim._mask[:, c].astype(np.uint8) << c
-        self.fixed = bool(bits.any())
-        self.mask = torch.from_numpy(bits).to(_dev())
+    def __init__(self, sim, needs="natural frequencies need"):
+        super().__init__(sim, needs)
+        self.n = self.nnode * self.N
 
     def head(self):
-        return (self.N, self._nelems.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _dp(self.h))
+        return super().head(_dp(self.h))
 
     def block(self, X):
         """``X`` as a device block [columns, numNodes, N] (one vector [numNodes, N] is a block of one column)"""
@@ -423,8 +404,7 @@ class MeanEigenvalueObjective:
         if self._grad is None:
             sim, g = self._sim, _Grid(self._sim)
             rho = sim.getDensities_device()[:g.nelem]
-            gamma = float(sim.gamma)
-            dE = (gamma * rho ** (gamma - 1.0) * (float(sim.E_0) - float(sim.E_min))).contiguous()
+            dE = simp_multipliers(sim, rho)[1]
             dm = _mass_law(rho, **self.mass)[1]
             K0 = np.ascontiguousarray(sim.fullDensityElementStiffnessMatrix())
             cK, cM = np.ascontiguousarray(-self._lam ** -2.0), np.ascontiguousarray(1.0 / self._lam)
@@ -439,23 +419,12 @@ class MeanEigenvalueObjective:
         return _to_np(self.gradient_device())
 
 
-class MeanEigenvalueFunction(torch.autograd.Function):
+class MeanEigenvalueFunction(ObjectiveFunction):
     """J of the predicted densities as an autograd node, the counterpart of ``stress.PNormStressFunction``: forward sets the
     densities and solves the eigenproblem; backward is ``gradient_device()`` weighted by the incoming gradient."""
 
-    @staticmethod
-    def forward(ctx, densities, objective):
-        objective.updateCache(densities.detach().reshape(-1))
-        ctx.objective, ctx.u, ctx.dtype, ctx.shape = objective, objective.modes_device(), densities.dtype, densities.shape
-        return torch.tensor(objective.evaluate(), dtype=torch.float64, device=densities.device)
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        obj = ctx.objective
-        if obj.modes_device() is not ctx.u:
-            raise RuntimeError("meanEigenvalue: the objective was updated between forward and backward")
-        g = float(grad_output.detach().cpu()) * obj.gradient_device()
-        return g.to(ctx.dtype).reshape(ctx.shape), None
+    NAME = "meanEigenvalue"
+    field = staticmethod(lambda objective: objective.modes_device())
 
 
 def meanEigenvalue(densities, objective):

@@ -23,35 +23,30 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._grid import Grid, ObjectiveFunction, _dp, simp_multipliers
 from .pyVoxelFEM import _dev, _ptr, _stream, _to_dev, _to_np
 
 __all__ = ["elementStrains", "elementStrains_device", "elementStresses", "elementStresses_device", "vonMises", "vonMises_device",
            "PNormStressObjective", "PNormStressFunction", "pNormStress", "complianceAndPNormStress"]
 
 
-def _dp(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+def _exponent(sim, stressExponent):
+    q = float(sim.gamma if stressExponent is None else stressExponent)
+    if not q > 0.0:
+        raise RuntimeError("stressExponent must be positive (got %r)" % (stressExponent,))
+    return q
 
 
-class _Grid:
+class _Grid(Grid):
     """what every ``vfem_stress_*`` grid call starts with, taken from a simulator: the grid, the voxel's edge lengths, the tensor"""
 
     def __init__(self, sim):
-        N = getattr(sim, "N", None)
-        if N not in (2, 3) or getattr(sim, "P", None) != 1:
-            raise RuntimeError("element stresses need a degree-1 simulator (TensorProductSimulator1_1 or 1_1_1)")
-        if sim._num_stored_elements() != sim.numElements():
-            raise RuntimeError("element stresses need a whole grid: this simulator stores slab padding layers")
-        self.sim = sim
-        self.N, self.S = N, 3 if N == 2 else 6
-        self.ne = [int(n) for n in sim.NbElementsPerDimension()]
-        self.nelem, self.nnode = sim.numElements(), sim.numNodes()
-        self.h = np.ascontiguousarray((sim._bbmax - sim._bbmin) / np.asarray(self.ne, dtype=np.float64))
+        super().__init__(sim, "element stresses need")
+        self.S = 3 if self.N == 2 else 6
         self.D = np.ascontiguousarray(sim.ETensor.D)
-        self._nelems = np.asarray(self.ne, dtype=np.int64)
 
     def head(self):
-        return (self.N, self._nelems.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), _dp(self.h), _dp(self.D))
+        return super().head(_dp(self.h), _dp(self.D))
 
     def displacement(self, u):
         """``u`` as a device tensor [numNodes, N] (a contiguous float64 device tensor is taken as it is)"""
@@ -63,12 +58,7 @@ class _Grid:
     def multipliers(self, stressExponent):
         """(m, dm/drho) of the simulator's densities: m = E_min + rho^q (E_0 - E_min)"""
         sim = self.sim
-        q = float(sim.gamma if stressExponent is None else stressExponent)
-        if not q > 0.0:
-            raise RuntimeError("stressExponent must be positive (got %r)" % (stressExponent,))
-        rho = sim.getDensities_device()[:self.nelem]
-        E0, Emin = float(sim.E_0), float(sim.E_min)
-        return (Emin + rho ** q * (E0 - Emin)).contiguous(), (q * rho ** (q - 1.0) * (E0 - Emin)).contiguous()
+        return simp_multipliers(sim, sim.getDensities_device()[:self.nelem], _exponent(sim, stressExponent))
 
     def fields(self, u, m, strain=False, stress=False, vm=False):
         new = lambda want, *shape: torch.empty(shape, dtype=torch.float64, device=_dev()) if want else None
@@ -190,14 +180,10 @@ class PNormStressObjective:
         """dJ/du at fixed densities, [numNodes, N], zero at the Dirichlet components"""
         st = self._need()
         if st["a"] is None:
-            g, sim = st["grid"], self._sim
-            bits = np.zeros(g.nnode, dtype=np.uint8)
-            for c in range(g.N):
-                bits |= sim._mask[:, c].astype(np.uint8) << c
-            mask = torch.from_numpy(bits).to(_dev())
+            g = st["grid"]
             a = torch.empty((g.nnode, g.N), dtype=torch.float64, device=_dev())
             work = torch.empty((g.nelem, g.S), dtype=torch.float64, device=_dev())          # scratch of the call
-            _lib.check(_lib.load().vfem_stress_adjoint_load(*g.head(), _ptr(st["m"]), _ptr(st["u"]), st["J"], self.P, _ptr(mask),
+            _lib.check(_lib.load().vfem_stress_adjoint_load(*g.head(), _ptr(st["m"]), _ptr(st["u"]), st["J"], self.P, _ptr(g.mask),
                                                             _ptr(work), _ptr(a), _stream()))
             st["a"] = a
         return st["a"]
@@ -223,9 +209,7 @@ class PNormStressObjective:
         if st["grad"] is None:
             g, sim = st["grid"], self._sim
             lam = self.adjoint_device()
-            rho = sim.getDensities_device()[:g.nelem]
-            gamma = float(sim.gamma)
-            dE = (gamma * rho ** (gamma - 1.0) * (float(sim.E_0) - float(sim.E_min))).contiguous()
+            dE = simp_multipliers(sim, sim.getDensities_device()[:g.nelem])[1]
             K0 = np.ascontiguousarray(sim.fullDensityElementStiffnessMatrix())
             out = torch.empty(g.nelem, dtype=torch.float64, device=_dev())
             _lib.check(_lib.load().vfem_stress_pnorm_gradient(*g.head(), _dp(K0), _ptr(st["m"]), _ptr(st["dm"]), _ptr(dE), _ptr(st["u"]),
@@ -237,22 +221,23 @@ class PNormStressObjective:
         return _to_np(self.gradient_device())
 
 
-class PNormStressFunction(torch.autograd.Function):
+class PNormStressFunction(ObjectiveFunction):
     """(compliance, J) of the predicted densities as one autograd node, the stress counterpart of ``fem.VoxelFEMFunction``: forward
     sets the densities and solves once; backward is the two gradients weighted by the incoming gradient (the stress gradient costs
     its adjoint solve only where its weight is not zero)."""
 
-    @staticmethod
-    def forward(ctx, densities, objective):
-        objective.updateCache(densities.detach().reshape(-1))
-        ctx.objective, ctx.u, ctx.dtype, ctx.shape = objective, objective.solved._u, densities.dtype, densities.shape
+    NAME = "pNormStress"
+    field = staticmethod(lambda objective: objective.solved._u)
+
+    @classmethod
+    def forward(cls, ctx, densities, objective):
+        cls.update(ctx, densities, objective)
         return torch.tensor([objective.solved.compliance(), objective.evaluate()], dtype=torch.float64, device=densities.device)
 
-    @staticmethod
-    def backward(ctx, grad_output):
+    @classmethod
+    def backward(cls, ctx, grad_output):
+        cls.refuse_stale(ctx)
         obj = ctx.objective
-        if obj.solved._u is not ctx.u:
-            raise RuntimeError("pNormStress: the objective was updated between forward and backward")
         wc, ws = (float(v) for v in grad_output.detach().cpu())
         g = torch.zeros(ctx.shape, dtype=torch.float64, device=grad_output.device).reshape(-1)
         if ws != 0.0:

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._grid import ObjectiveFunction, _dp
 from .pyVoxelFEM import _dev, _ptr, _stream, _to_dev, _to_np
 
 __all__ = ["HeatConductionSimulator", "ThermalComplianceObjective", "PNormTemperatureObjective", "ThermalComplianceFunction",
@@ -37,10 +38,6 @@ __all__ = ["HeatConductionSimulator", "ThermalComplianceObjective", "PNormTemper
 
 MAX_COLUMNS = 8
 _TILE = 64
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
 def conductivityMatrix(k, h):
@@ -570,44 +567,13 @@ class PNormTemperatureObjective:
         return _to_np(self.gradient_device())
 
 
-class _ObjectiveFunction(torch.autograd.Function):
-    """an objective of this module as an autograd node, the counterpart of ``loadcases.AggregateComplianceFunction``: forward sets
-    the densities and solves; backward is ``gradient_device()`` weighted by the incoming gradient"""
-
-    NAME = "thermal"
-
-    @staticmethod
-    def forward(ctx, densities, objective):
-        objective.updateCache(densities.detach().reshape(-1))
-        ctx.objective, ctx.u, ctx.dtype, ctx.shape = objective, objective._u, densities.dtype, densities.shape
-        return torch.tensor(objective.evaluate(), dtype=torch.float64, device=densities.device)
-
-    @classmethod
-    def _backward(cls, ctx, grad_output):
-        obj = ctx.objective
-        if obj._u is None or obj._u is not ctx.u:
-            raise RuntimeError("%s: the objective was updated between forward and backward" % cls.NAME)
-        w = float(grad_output.detach().cpu())
-        g = obj.gradient_device()
-        if w != 1.0:
-            g = w * g
-        return g.to(ctx.dtype).reshape(ctx.shape), None
-
-
-class ThermalComplianceFunction(_ObjectiveFunction):
+# the two objectives as autograd nodes, the counterparts of ``loadcases.AggregateComplianceFunction``
+class ThermalComplianceFunction(ObjectiveFunction):
     NAME = "thermalCompliance"
 
-    @staticmethod
-    def backward(ctx, grad_output):
-        return ThermalComplianceFunction._backward(ctx, grad_output)
 
-
-class PNormTemperatureFunction(_ObjectiveFunction):
+class PNormTemperatureFunction(ObjectiveFunction):
     NAME = "pNormTemperature"
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        return PNormTemperatureFunction._backward(ctx, grad_output)
 
 
 def thermalCompliance(densities, objective):
