@@ -762,6 +762,34 @@ int vfem_thermal_mg_vcycle(vfem_thermal_mg *h, const double *B, double *X, int s
 int vfem_thermal_mg_pcg(vfem_thermal_mg *h, const double *b, double *x, double tol, int max_iter, int smoothing,
                         int *iterations_out_host, double *relres_out_host, void *stream);
 
+/* ---- thermo-elastic coupling of a degree-1 grid: a temperature field as a load, its transpose, its gradient ----
+ * Handle-free, dim = 2 or 3.  The three entry points start as the load-case section's do; the node mask, the numbering and the
+ * alignment rule are those of that section.  E, dE, g_in, g_out (device) are [elements], T and q (device) are [node], f_in, f_out
+ * (device) are [node][dim], U (device) is the block [case][node][dim].  A coupling matrix G (host) is row-major [ke = dim 2^dim]
+ * [npe = 2^dim], dof = dim node + component in the local node order of K0:
+ *   G[(n, a)][m] = int beta_aq dN_n/dx_q N_m dV,  beta = C : alpha  (the temperature is interpolated inside the element).
+ * vfem_thermoelastic_load: f_out = P (f_in + sum_e E[e] G (T_e - T_ref)).  f_in and mask may be NULL (zero; P = I).  f_out may be
+ *   f_in; it overlaps nothing else.  One thread per node gathers its 2^dim elements in ascending local-node order; G travels in
+ *   the kernel arguments.  Asynchronous.
+ * vfem_thermoelastic_adjoint_source: q = P_T sum_i a_host[i] sum_e E[e] G_i^T u_ie over the ncases (1 .. 8) columns of U, G_host
+ *   [ncases][ke][npe]: the transpose of the load, the source of the thermal adjoint.  fixed (one byte per node, nonzero = fixed
+ *   temperature; may be NULL) zeroes q there.  Cases, then elements, then rows ascending.  q overlaps no input.  It uploads the
+ *   matrices and synchronises the stream, as vfem_loads_gradient does.
+ * vfem_thermoelastic_gradient: g_out[e] = g_in[e] + dE[e] sum_i a_host[i] u_ie^T G_i (T_e - Tref_host[i]).  g_in may be NULL
+ *   (zero); g_out may be g_in and overlaps nothing else.  One thread per element reads its temperatures once for all cases.  It
+ *   uploads the matrices and synchronises the stream.
+ * No atomics, fixed summation order: results are bit-identical run to run.
+ * Refused before any device call: NULL pointers where one is required, dim not 2 or 3, extents < 1, h <= 0, ncases out of range,
+ * non-finite matrices, coefficients or reference temperatures, and the overlaps named above. */
+int vfem_thermoelastic_load(int dim, const int64_t *nelems_host, const double *h_host, const double *G_host, double T_ref,
+                            const double *E, const double *T, const uint8_t *mask, const double *f_in, double *f_out, void *stream);
+int vfem_thermoelastic_adjoint_source(int dim, const int64_t *nelems_host, const double *h_host, int ncases, const double *a_host,
+                                      const double *G_host, const double *E, const double *U, const uint8_t *fixed, double *q,
+                                      void *stream);
+int vfem_thermoelastic_gradient(int dim, const int64_t *nelems_host, const double *h_host, int ncases, const double *a_host,
+                                const double *G_host, const double *Tref_host, const double *dE, const double *T, const double *U,
+                                const double *g_in, double *g_out, void *stream);
+
 /* ---- timers: BENCHMARK_* registry (MeshFEM GlobalBenchmark.hh / Timer.hh; VoxelFEM.cc:245-255) ---- */
 int vfem_timers_reset(void);
 int vfem_timers_report(char *buf_host, size_t buf_len);

@@ -4,7 +4,7 @@ __version__ = "0.1.0"
 
 from .materials import ElasticityTensor  # noqa: E402,F401  (numpy only: importing the package still loads neither torch nor the library)
 
-_LAZY = ("stress", "mma", "modal", "buckling", "loadcases", "thermal")     # modules that load torch and the library: imported on first use, so that `import ndr_amd` stays light
+_LAZY = ("stress", "mma", "modal", "buckling", "loadcases", "thermal", "thermoelastic") # modules that load torch and the library: imported on first use, so that `import ndr_amd` stays light
 
 
 def __getattr__(name):

@@ -251,6 +251,11 @@ SIGNATURES = {
     "vfem_thermal_mg_prolong_add": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "vfem_thermal_mg_vcycle": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "vfem_thermal_mg_pcg": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_int, c_int, POINTER(c_int), POINTER(c_double), c_void_p]),
+    "vfem_thermoelastic_load": (c_int, _MODAL + [POINTER(c_double), c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vfem_thermoelastic_adjoint_source": (c_int, _MODAL + [c_int, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p,
+                                                           c_void_p, c_void_p]),
+    "vfem_thermoelastic_gradient": (c_int, _MODAL + [c_int, POINTER(c_double), POINTER(c_double), POINTER(c_double), c_void_p, c_void_p,
+                                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     "vfem_timers_reset": (c_int, []),
     "vfem_timers_report": (c_int, [c_char_p, c_size_t]),
 }

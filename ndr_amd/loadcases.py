@@ -27,6 +27,10 @@ E_min) the modulus of K, s_nq = +1 / -1 on the upper / lower face of axis q.  Wi
 With fixed loads only the gradient is nowhere positive and ``OCOptimizer`` works.  With self-weight or an eigenstrain it has both
 signs (material added above a span weighs on it; on a 16 x 6 arch under its own weight tests/test_loadcases_cpu.py pins the
 counts): use ``ndr_amd.mma.MMAOptimizer`` or ``aggregateCompliance`` with a torch optimiser.
+
+A case may also carry the solved temperature field of a heat-conduction problem (``LoadCase(temperature=TemperatureLoad(...))``,
+``ndr_amd.thermoelastic``): its load gains sum_e E(rho_e) G_i (T_e - T_ref), the objective solves the heat problem once per
+design before it assembles, and the gradient gains dE_e u_ie^T G_i theta_e and the term of one thermal adjoint solve.
 """
 import numpy as np
 import torch
@@ -68,9 +72,10 @@ class LoadCase:
     """One load case.  ``loads``: the fixed nodal load [numNodes, N] (numpy or device), ``None`` for the simulator's own
     ``buildLoadVector_device()`` (read when the case is handed to an objective or assembled), ``0`` for none.  ``acceleration``:
     N values g; the body force m(rho) g.  ``eigenstrain``: a symmetric N x N strain eps* the material would take on unloaded
-    (``thermalStrain``); the load int B^T E(rho) C : eps*.  ``weight``: w_i > 0 in the aggregate."""
+    (``thermalStrain``); the load int B^T E(rho) C : eps*.  ``temperature``: a ``thermoelastic.TemperatureLoad``, the solved
+    temperature field of a heat-conduction problem as a thermal load.  ``weight``: w_i > 0 in the aggregate."""
 
-    def __init__(self, loads=None, acceleration=None, eigenstrain=None, weight=1.0):
+    def __init__(self, loads=None, acceleration=None, eigenstrain=None, weight=1.0, temperature=None):
         self.loads = loads
         self.acceleration = None if acceleration is None else np.array(acceleration, dtype=np.float64).reshape(-1)
         self.eigenstrain = None if eigenstrain is None else np.array(eigenstrain, dtype=np.float64)
@@ -83,10 +88,15 @@ class LoadCase:
             e = self.eigenstrain
             if e.ndim != 2 or e.shape[0] != e.shape[1] or not np.isfinite(e).all() or np.abs(e - e.T).max() > 1e-12 * max(np.abs(e).max(), 1e-300):
                 raise RuntimeError("LoadCase: eigenstrain must be a finite symmetric N x N matrix")
+        self.temperature = temperature
+        if temperature is not None:
+            from . import thermoelastic
+            if not isinstance(temperature, thermoelastic.TemperatureLoad):
+                raise TypeError("LoadCase: temperature is a thermoelastic.TemperatureLoad (got %r)" % (type(temperature).__name__,))
 
     @property
     def designDependent(self):
-        return self.acceleration is not None or self.eigenstrain is not None
+        return self.acceleration is not None or self.eigenstrain is not None or self.temperature is not None
 
     def _has_fixed(self):
         return not (self.loads is not None and not isinstance(self.loads, torch.Tensor) and np.ndim(self.loads) == 0
@@ -169,6 +179,9 @@ def assembleLoad_device(sim, case, mass=None):
     case = _check_case(case)
     Lb, Lt = g.patterns(case)
     F = g.fixed_load(case)
+    if case.temperature is not None:
+        raise RuntimeError("assembleLoad: a case with a temperature field is assembled by LoadCaseComplianceObjective (its load "
+                           "follows a heat solve)")
     if F is None and Lb is None and Lt is None:
         return torch.zeros((g.nnode, g.N), dtype=torch.float64, device=_dev())
     rho = sim.getDensities_device()[:g.nelem]
@@ -244,7 +257,9 @@ class LoadCaseComplianceObjective:
     those of ``MultigridComplianceObjective``), each case warm-started from its own last displacement; the hierarchy follows the
     densities once per design (a solve on unchanged moduli keeps it).  ``aggregate`` is "sum" or "pnorm" (``P`` >= 1; a smooth upper
     bound of the worst weighted case, max <= J <= k^(1/P) max).  ``mass``: the keywords of ``modal.massMultipliers`` for the
-    self-weight.  The fixed loads are read at construction.  The constructor solves once unless ``skipSolve``.
+    self-weight.  The fixed loads are read at construction.  The constructor solves once unless ``skipSolve``.  Heated cases
+    (``LoadCase(temperature=...)``) share one ``ThermalComplianceObjective``: every update solves it first, at the same densities, and
+    every gradient adds one thermal adjoint solve through it (``ndr_amd.thermoelastic``).
 
     The objective protocol of the design loop: ``updateCache(xPhys)``, ``evaluate()``, ``gradient_device()``, ``gradient()``;
     also ``compliances()`` (host, [k]), ``displacements_device()`` ([k, numNodes, N]), ``loads_device()``; ``_u`` is case 0's
@@ -286,6 +301,16 @@ class LoadCaseComplianceObjective:
         stack = lambda j: None if all(p[j] is None for p in self._patterns) else \
             np.ascontiguousarray(np.stack([np.zeros(g.ke) if p[j] is None else p[j] for p in self._patterns]))
         self._Lb, self._Lt = stack(0), stack(1)
+        # the heated cases: one heat solve for all of them, a coupling matrix and a reference temperature each
+        heated = [c.temperature for c in self._cases if c.temperature is not None]
+        self._thermal = heated[0].thermal if heated else None
+        for t in heated:
+            if t.thermal is not self._thermal:
+                raise RuntimeError("LoadCaseComplianceObjective: the heated cases of one objective share one ThermalComplianceObjective "
+                                   "(several temperature fields are not supported)")
+            t.check(self._sim)
+        self._G = [None if c.temperature is None else c.temperature.couplingMatrix(self._sim) for c in self._cases]
+        self._tref = [0.0 if c.temperature is None else c.temperature.referenceTemperature for c in self._cases]
         self._views = [_CaseView(self, i) for i in range(k)]
         self._state = None
         if not skipSolve:
@@ -322,6 +347,10 @@ class LoadCaseComplianceObjective:
         if self._Lb is not None:
             m, dm = modal._mass_law(rho, **self.mass)
         E, dE = g.stiffness_multipliers(rho)
+        T = None
+        if self._thermal is not None:               # the heat problem at the same densities, solved once for all heated cases
+            self._thermal.updateCache(rho)
+            T = self._thermal._u
         last = None if self._state is None else self._state["us"]
         k = len(self._cases)
         U = torch.empty((k, g.nnode, g.N), dtype=torch.float64, device=_dev())
@@ -333,6 +362,9 @@ class LoadCaseComplianceObjective:
                 f = torch.zeros((g.nnode, g.N), dtype=torch.float64, device=_dev())
             else:
                 f = g.assemble(F, Lb, Lt, m, E)
+            if self._G[i] is not None:
+                _lib.check(_lib.load().vfem_thermoelastic_load(*g.head(), _dp(self._G[i]), self._tref[i], _ptr(E), _ptr(T),
+                                                               _ptr(g.mask), _ptr(f), _ptr(f), _stream()))
             fs.append(f)
             U[i].copy_(self._solve(f, None if last is None else last[i]))
             if self._mg is not None:
@@ -351,7 +383,8 @@ class LoadCaseComplianceObjective:
                 a = self._weights * (wc / J) ** (self.P - 1.0)
             else:
                 J, a = 0.0, np.zeros(k)
-        self._state = dict(grid=g, U=U, us=us, fs=fs, c=c, J=J, a=a, dE=dE, dm=dm, iterations=iterations, grad=None)
+        self._state = dict(grid=g, U=U, us=us, fs=fs, c=c, J=J, a=a, dE=dE, dm=dm, iterations=iterations, grad=None,
+                           E=E, T=T)
 
     def _need(self):
         if self._state is None:
@@ -408,7 +441,26 @@ class LoadCaseComplianceObjective:
         _lib.check(_lib.load().vfem_loads_gradient(*g.head(), len(idx), _dp(K0), _dp(cK), _dp(cB), _dp(cT), _dp(Lb), _dp(Lt),
                                                    _ptr(st["dE"]), _ptr(st["dm"]) if Lb is not None else None, _ptr(U), _ptr(out),
                                                    _stream()))
+        hot = [j for j in idx if self._G[j] is not None]
+        if hot:
+            self._add_coupled_terms(st, a[[idx.index(j) for j in hot]], hot, out)
         return out
+
+    def _add_coupled_terms(self, st, a, hot, out):
+        """onto ``out``: dE_e sum_i a_i u_ie^T G_i theta_e - kappa'_e mu_e^T Kc0 T_e over the heated cases ``hot``, A mu = P_T sum_i
+        a_i sum_e E_e G_i^T u_ie: one thermal adjoint solve through the thermal objective's own solver"""
+        g, heat, lib = st["grid"], self._thermal._sim, _lib.load()
+        a = np.ascontiguousarray(a)
+        G = np.ascontiguousarray(np.stack([self._G[j] for j in hot]))
+        tref = np.ascontiguousarray(np.array([self._tref[j] for j in hot], dtype=np.float64))
+        U = st["us"][hot[0]] if len(hot) == 1 else (st["U"] if len(hot) == len(self._cases) else st["U"][hot].contiguous())
+        _lib.check(lib.vfem_thermoelastic_gradient(*g.head(), len(hot), _dp(a), _dp(G), _dp(tref), _ptr(st["dE"]), _ptr(st["T"]),
+                                                   _ptr(U), _ptr(out), _ptr(out), _stream()))
+        q = torch.empty(g.nnode, dtype=torch.float64, device=_dev())
+        _lib.check(lib.vfem_thermoelastic_adjoint_source(*g.head(), len(hot), _dp(a), _dp(G), _ptr(st["E"]), _ptr(U), heat._fixed(),
+                                                         _ptr(q), _stream()))
+        mu = self._thermal._solve(q)
+        out += heat.bilinearGradient_device([-1.0], mu.unsqueeze(0), st["T"].unsqueeze(0))
 
     def gradient_device(self):
         st = self._need()
