@@ -790,6 +790,50 @@ int vfem_thermoelastic_gradient(int dim, const int64_t *nelems_host, const doubl
                                 const double *G_host, const double *Tref_host, const double *dE, const double *T, const double *U,
                                 const double *g_in, double *g_out, void *stream);
 
+/* ---- transient heat conduction on a degree-1 grid: capacity operator, solver, time-accumulated gradient ----
+ * Handle-free, dim = 2 or 3; grid, numbering, mask and alignment rule are those of the steady section.  cap, dcap (device) are
+ * [elements] beside kappa, dkappa.  The capacity matrix of a voxel is M[a][b] = m[popcount(a xor b)], a function of the number of axes
+ * along which two local nodes differ, so it is passed as m_host[dim + 1] (consistent: capacity vol 2^(dim - d) / 6^dim; lumped: vol /
+ * 2^dim at d = 0 and zero elsewhere).  The two-term operator is
+ *   A(Ka, mb) = P (sum_e kappa[e] Ka + sum_e cap[e] M(mb)) P + iota (I - P),
+ * and the caller folds the scalars of the theta-scheme into Ka_host [2^dim][2^dim] and mb_host [dim + 1]: Ka = theta Kc0, mb = m / dt
+ * for the system operator of a step, Ka = -(1 - theta) Kc0, mb = m / dt for its right-hand side.
+ * vfem_transient_apply: Y_c = A X_c + P b_c for the ncols (1 .. 8) columns; b (a block like X) may be NULL.  identity = iota, 0 or 1:
+ *   what a fixed node keeps of its own value.  With b and identity = 0 this is the right-hand side of a step in one pass.  One
+ *   thread per node forms its 3^dim couplings of both terms once for all columns.  Y overlaps no input.  Asynchronous.
+ * vfem_transient_diagonal: diag = the diagonal of A with iota = 1 (1 at a fixed node).  Asynchronous.
+ * vfem_transient_band_assemble: the lower band of A with iota = 1, in the layout and with the n, w of vfem_thermal_band_assemble.
+ *   Asynchronous.
+ * vfem_transient_pcg: vfem_thermal_pcg on A(Ka, mb) x = b with iota = 1: the same loop, stopping rule, outputs and two errors; the
+ *   operator is positive definite without a fixed node when theta, dt and the capacities are positive.  Synchronises the stream.
+ * vfem_transient_gradient: with T and Lam (device) the blocks [steps + 1][node] of a march and of its adjoint (row 0 of Lam is not read),
+ *   g[e] = -sum_{n = 1 .. steps} (dcap[e] / dt lam_e^n . M(m) (T_e^n - T_e^(n-1)) + dkappa[e] lam_e^n . Kc0 (theta T_e^n + (1 - theta) T_e^(n-1))).
+ *   One thread per element marches the steps with the temperatures of the step before in registers; steps has no upper limit but
+ *   memory.  g overlaps no input.  Asynchronous.
+ * vfem_transient_mg_create: vfem_thermal_mg_create for A(Ka, mb): the handle it returns has the two-term operator (iota = 1) as its
+ *   level 0, matrix-free from kappa and cap, which it keeps as it keeps kappa and fixed; the Galerkin levels, the coarsest solve and
+ *   every vfem_thermal_mg_* call (level_apply, smooth, vcycle, pcg, destroy, ...) are those of that section, unchanged.  One hierarchy
+ *   serves every step of a march and of its adjoint.  Create synchronises the stream.
+ * No atomics, fixed summation order: results are bit-identical run to run.
+ * Refused before any device call: NULL pointers where one is required, dim not 2 or 3, extents < 1, a non-finite Ka, Kc0, mb or m,
+ * identity not 0 or 1, a column count out of range, steps < 1, dt <= 0, theta outside [0.5, 1], tol <= 0, max_iter < 1, and the
+ * overlaps named above. */
+int vfem_transient_apply(int dim, const int64_t *nelems_host, const double *Ka_host, const double *mb_host, const double *kappa,
+                         const double *cap, const uint8_t *fixed, int identity, int ncols, const double *X, const double *b, double *Y,
+                         void *stream);
+int vfem_transient_diagonal(int dim, const int64_t *nelems_host, const double *Ka_host, const double *mb_host, const double *kappa,
+                            const double *cap, const uint8_t *fixed, double *diag, void *stream);
+int vfem_transient_band_assemble(int dim, const int64_t *nelems_host, const double *Ka_host, const double *mb_host, const double *kappa,
+                                 const double *cap, const uint8_t *fixed, double *band, void *stream);
+int vfem_transient_pcg(int dim, const int64_t *nelems_host, const double *Ka_host, const double *mb_host, const double *kappa,
+                       const double *cap, const uint8_t *fixed, const double *b, double *x, double tol, int max_iter,
+                       int *iterations_out_host, double *relres_out_host, void *stream);
+int vfem_transient_mg_create(vfem_thermal_mg **out, int dim, const int64_t *nelems_host, const double *Ka_host, const double *mb_host,
+                             const double *kappa, const double *cap, const uint8_t *fixed, int max_coarsenings, void *stream);
+int vfem_transient_gradient(int dim, const int64_t *nelems_host, int64_t steps, const double *Kc0_host, const double *m_host, double dt,
+                            double theta, const double *dkappa, const double *dcap, const double *T, const double *Lam, double *g,
+                            void *stream);
+
 /* ---- timers: BENCHMARK_* registry (MeshFEM GlobalBenchmark.hh / Timer.hh; VoxelFEM.cc:245-255) ---- */
 int vfem_timers_reset(void);
 int vfem_timers_report(char *buf_host, size_t buf_len);

@@ -38,6 +38,9 @@ _MODAL = [c_int, POINTER(c_int64), POINTER(c_double)]
 # what every vfem_thermal_* entry point starts with: dim, nelems (host)
 _THERMAL = [c_int, POINTER(c_int64)]
 
+# what every vfem_transient_* operator call starts with: dim, nelems, Ka, mb (host), kappa, cap, fixed (device)
+_TRANSIENT = _THERMAL + [POINTER(c_double), POINTER(c_double), c_void_p, c_void_p, c_void_p]
+
 # name -> (restype, argtypes); kept in one table so tests can check it against include/vfem.h
 SIGNATURES = {
     "vfem_last_error": (c_char_p, []),
@@ -256,6 +259,13 @@ SIGNATURES = {
                                                            c_void_p, c_void_p]),
     "vfem_thermoelastic_gradient": (c_int, _MODAL + [c_int, POINTER(c_double), POINTER(c_double), POINTER(c_double), c_void_p, c_void_p,
                                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vfem_transient_apply": (c_int, _TRANSIENT + [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vfem_transient_diagonal": (c_int, _TRANSIENT + [c_void_p, c_void_p]),
+    "vfem_transient_band_assemble": (c_int, _TRANSIENT + [c_void_p, c_void_p]),
+    "vfem_transient_pcg": (c_int, _TRANSIENT + [c_void_p, c_void_p, c_double, c_int, POINTER(c_int), POINTER(c_double), c_void_p]),
+    "vfem_transient_mg_create": (c_int, [POINTER(c_void_p)] + _TRANSIENT + [c_int, c_void_p]),
+    "vfem_transient_gradient": (c_int, _THERMAL + [c_int64, POINTER(c_double), POINTER(c_double), c_double, c_double, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p]),
     "vfem_timers_reset": (c_int, []),
     "vfem_timers_report": (c_int, [c_char_p, c_size_t]),
 }

@@ -4,8 +4,9 @@
 //
 // All fp64, one double per access (8-byte alignment is enough), no atomics: one thread owns what it writes and sums in a fixed order,
 // so two runs give the same bits.  A level's couplings come from a source: ThermalFineSrc forms them from the node's 2^N
-// conductivities as k_thermal_apply does (thermal_couplings, thermal_device.h), ThermalStoredSrc loads A[offset][node] (coalesced
-// over the nodes of a wave).  Both give the 3^N coefficients, the neighbour distances and the bits of the neighbours that take part.
+// conductivities as k_thermal_apply does (thermal_couplings, thermal_device.h), ThermalTwoTermSrc adds the capacity term of a
+// transient step's operator in separate instantiations, ThermalStoredSrc loads A[offset][node] (coalesced over the
+// nodes of a wave).  Both give the 3^N coefficients, the neighbour distances and the bits of the neighbours that take part.
 //
 // Level-0 colour sweep (the hot path: two sweeps of 2^N colours per cycle over all fine nodes): one thread per node of the colour,
 // 64 x 4 blocks over the colour's sub-grid with the lanes along the last axis.  The lanes of a wave touch every second double of a
@@ -31,6 +32,18 @@ struct ThermalFineSrc {
     __device__ __forceinline__ void couplings(const ModalGrid &g, const int (&c)[N], long long node,
                                               double (&coef)[ThermalTraits<N>::NB]) const {
         thermal_couplings<N>(g, K, kappa, c, coef);
+    }
+};
+
+// level 0 of a transient step's hierarchy: both terms (transient_couplings, thermal_device.h)
+struct ThermalTwoTermSrc {
+    ThermalMatrix K;
+    ThermalCapacity mb;
+    const double *kappa, *cap;
+    template <int N>
+    __device__ __forceinline__ void couplings(const ModalGrid &g, const int (&c)[N], long long node,
+                                              double (&coef)[ThermalTraits<N>::NB]) const {
+        transient_couplings<N>(g, K, mb, kappa, cap, c, coef);
     }
 };
 
@@ -312,7 +325,10 @@ void launch_thermal_mg_galerkin(const ModalGrid &fine, const ModalGrid &coarse, 
     const GsColor all = all_nodes(coarse);
     const dim3 grd(flat_blocks(all), fine.N == 2 ? 9 : 27);
 #define ARGS(SRC) <<<grd, MG_T, 0, s>>>(fine, coarse, SRC, all, fixed_f, fixed_c, Ac)
-    if (src.kappa) {
+    if (src.cap) {
+        const ThermalTwoTermSrc f{*src.K, *src.mb, src.kappa, src.cap};
+        THERMAL_MG_DISPATCH(fine, (k_thermal_mg_galerkin<2, ThermalTwoTermSrc> ARGS(f)), (k_thermal_mg_galerkin<3, ThermalTwoTermSrc> ARGS(f)));
+    } else if (src.kappa) {
         const ThermalFineSrc f{*src.K, src.kappa};
         THERMAL_MG_DISPATCH(fine, (k_thermal_mg_galerkin<2, ThermalFineSrc> ARGS(f)), (k_thermal_mg_galerkin<3, ThermalFineSrc> ARGS(f)));
     } else {
@@ -339,7 +355,13 @@ void launch_thermal_mg_apply(const ModalGrid &g, const double *A, const uint8_t 
 
 void launch_thermal_mg_sweep_colour(const ModalGrid &g, const ThermalLevelOp &src, const uint8_t *fixed, const double *dinv,
                                     const GsColor &colour, double *x, const double *b, hipStream_t s) {
-    if (src.kappa) {
+    if (src.cap) {
+        const ThermalTwoTermSrc f{*src.K, *src.mb, src.kappa, src.cap};
+        const dim3 grd = cell_blocks(g.N, colour);
+#define ARGS <<<grd, cell_block(), 0, s>>>(g, f, fixed, dinv, colour, x, b, x)
+        THERMAL_MG_DISPATCH(g, (k_thermal_mg_level<2, MG_SWEEP, ThermalTwoTermSrc, true> ARGS), (k_thermal_mg_level<3, MG_SWEEP, ThermalTwoTermSrc, true> ARGS));
+#undef ARGS
+    } else if (src.kappa) {
         const ThermalFineSrc f{*src.K, src.kappa};
         const dim3 grd = cell_blocks(g.N, colour);
 #define ARGS <<<grd, cell_block(), 0, s>>>(g, f, fixed, dinv, colour, x, b, x)
@@ -372,7 +394,10 @@ void launch_thermal_mg_prolong_add(const ModalGrid &fine, const ModalGrid &coars
 void launch_thermal_mg_dense(const ModalGrid &g, const ThermalLevelOp &src, const uint8_t *fixed, double *M, hipStream_t s) {
     const GsColor all = all_nodes(g);
 #define ARGS(SRC) <<<flat_blocks(all), MG_T, 0, s>>>(g, SRC, all, fixed, M)
-    if (src.kappa) {
+    if (src.cap) {
+        const ThermalTwoTermSrc f{*src.K, *src.mb, src.kappa, src.cap};
+        THERMAL_MG_DISPATCH(g, (k_thermal_mg_dense<2, ThermalTwoTermSrc> ARGS(f)), (k_thermal_mg_dense<3, ThermalTwoTermSrc> ARGS(f)));
+    } else if (src.kappa) {
         const ThermalFineSrc f{*src.K, src.kappa};
         THERMAL_MG_DISPATCH(g, (k_thermal_mg_dense<2, ThermalFineSrc> ARGS(f)), (k_thermal_mg_dense<3, ThermalFineSrc> ARGS(f)));
     } else {

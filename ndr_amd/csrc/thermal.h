@@ -18,6 +18,8 @@ constexpr int THERMAL_MAX_NPE = 8;          // 2^N for N = 3
 
 struct ThermalMatrix { double k[THERMAL_MAX_NPE * THERMAL_MAX_NPE]; };      // Kc0, row-major 2^N x 2^N: 64 doubles in the kernel arguments
 struct ThermalCoef { double c[THERMAL_MAX_COLS]; };
+// the capacity matrix of the transient operator (transient.h): m[d], d = 0 .. N, the entry for two local nodes that differ along d axes
+struct ThermalCapacity { double m[4]; };
 struct ThermalTensor { double k[9]; };                                      // the conductivity tensor, row-major N x N
 
 // Y_c = A X_c, c < ncols: one thread per node forms its 3^N couplings once for all columns.  With b (ncols = 1): Y = b - A X.
@@ -61,6 +63,13 @@ ThermalMatrix thermal_element_matrix(const std::string &w, int dim, const double
 // the host reads the scalars before the first iteration and then every look_every iterations, stops when |r| / |b| <= tol, and
 // throws "not converged after ..." or "breakdown at iteration ..." with the residual.  The outputs are written in every case.
 using ThermalPreconditioner = std::function<void(const double *r, double *z)>;
+// The loop itself takes the operator as a callable (launched on s): out = A v, or with rhs out = rhs - A v; n = nodes, and
+// singular_because words what makes this operator singular for the breakdown message.  The form below is the steady operator's;
+// transient.hip hands in the two-term operator.
+using ThermalApply = std::function<void(const double *v, const double *rhs, double *out)>;
+void thermal_pcg(const std::string &w, long long n, const ThermalApply &apply, const char *singular_because, const double *b, double *x,
+                 double tol, int max_iter, int look_every, const ThermalPreconditioner &precondition, int *iterations_out_host,
+                 double *relres_out_host, hipStream_t s);
 void thermal_pcg(const std::string &w, const ModalGrid &g, const ThermalMatrix &K, const double *kappa, const uint8_t *fixed,
                  const double *b, double *x, double tol, int max_iter, int look_every, const ThermalPreconditioner &precondition,
                  int *iterations_out_host, double *relres_out_host, hipStream_t s);

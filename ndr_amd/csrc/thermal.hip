@@ -32,10 +32,9 @@ ThermalMatrix thermal_element_matrix(const std::string &w, int dim, const double
     return K;
 }
 
-void thermal_pcg(const std::string &w, const ModalGrid &g, const ThermalMatrix &K, const double *kappa, const uint8_t *fixed,
-                 const double *b, double *x, double tol, int max_iter, int look_every, const ThermalPreconditioner &precondition,
-                 int *iterations_out_host, double *relres_out_host, hipStream_t s) {
-    const long long n = g.nnode;
+void thermal_pcg(const std::string &w, long long n, const ThermalApply &apply, const char *singular_because, const double *b, double *x,
+                 double tol, int max_iter, int look_every, const ThermalPreconditioner &precondition, int *iterations_out_host,
+                 double *relres_out_host, hipStream_t s) {
     *iterations_out_host = 0;
     *relres_out_host = 0.0;
 
@@ -51,7 +50,7 @@ void thermal_pcg(const std::string &w, const ModalGrid &g, const ThermalMatrix &
         VFEM_HIP(hipStreamSynchronize(s));
     };
     launch_dot(n, b, b, scratch.p, sc.p + 4, s);
-    launch_thermal_apply(g, K, kappa, fixed, 1, x, b, r, s);            // r = b - A x
+    apply(x, b, r);                                                     // r = b - A x
     launch_dot(n, r, r, scratch.p, sc.p + 3, s);
     read();
     const double bb = host[4];
@@ -71,7 +70,7 @@ void thermal_pcg(const std::string &w, const ModalGrid &g, const ThermalMatrix &
         launch_dot(n, r, z, scratch.p, sc.p, s);
         launch_thermal_pcg_guard(sc.p, 0, it, s);
         launch_pcg_direction(n, z, d, sc.p, it == 1, s);
-        launch_thermal_apply(g, K, kappa, fixed, 1, d, nullptr, Ad, s);
+        apply(d, nullptr, Ad);
         launch_dot(n, d, Ad, scratch.p, sc.p + 2, s);
         launch_thermal_pcg_guard(sc.p, 1, it, s);
         launch_pcg_step_dot(n, x, r, d, Ad, sc.p, scratch.p, sc.p + 3, s);
@@ -82,8 +81,8 @@ void thermal_pcg(const std::string &w, const ModalGrid &g, const ThermalMatrix &
                 *iterations_out_host = (int) host[5];
                 *relres_out_host = std::sqrt(host[7] / bb);
                 snprintf(msg, sizeof msg, "%s: breakdown at iteration %d: p . Ap = %.3e is not positive (|r|/|b| = %.3e, tol %.3e); the "
-                         "operator is singular: no fixed node, a free node whose incident elements all have zero conductivity, or "
-                         "non-finite data", w.c_str(), (int) host[5], host[6], *relres_out_host, tol);
+                         "operator is singular: %s, or non-finite data", w.c_str(), (int) host[5], host[6], *relres_out_host, tol,
+                         singular_because);
                 throw Error(msg);
             }
             done = rr <= tol * tol * bb;
@@ -96,6 +95,14 @@ void thermal_pcg(const std::string &w, const ModalGrid &g, const ThermalMatrix &
         snprintf(msg, sizeof msg, "%s: not converged after %d iterations: |r|/|b| = %.3e (tol %.3e)", w.c_str(), it, *relres_out_host, tol);
         throw Error(msg);
     }
+}
+
+void thermal_pcg(const std::string &w, const ModalGrid &g, const ThermalMatrix &K, const double *kappa, const uint8_t *fixed,
+                 const double *b, double *x, double tol, int max_iter, int look_every, const ThermalPreconditioner &precondition,
+                 int *iterations_out_host, double *relres_out_host, hipStream_t s) {
+    const ThermalApply apply = [&](const double *v, const double *rhs, double *out) { launch_thermal_apply(g, K, kappa, fixed, 1, v, rhs, out, s); };
+    thermal_pcg(w, g.nnode, apply, "no fixed node, a free node whose incident elements all have zero conductivity", b, x, tol, max_iter,
+                look_every, precondition, iterations_out_host, relres_out_host, s);
 }
 
 }  // namespace vfem

@@ -14,11 +14,14 @@
 
 namespace vfem {
 
-// where a level's couplings come from: the stored stencil A (kappa null), or for level 0 the conductivities kappa and Kc0
+// where a level's couplings come from: the stored stencil A (kappa null), or for level 0 the conductivities kappa and Kc0; with
+// cap (the hierarchy of a transient step) level 0 is the two-term operator sum_e (kappa_e K + cap_e M(mb))
 struct ThermalLevelOp {
     const double *A;
     const double *kappa;
     const ThermalMatrix *K;         // host; read at the launch
+    const double *cap;              // null: the conduction term alone
+    const ThermalCapacity *mb;      // host; read at the launch
 };
 
 // coarse mask: fixed_c[I] = fixed_f[2 I]

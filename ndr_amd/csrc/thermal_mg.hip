@@ -6,6 +6,7 @@
 #include "grid_args.h"
 #include "mg_stored.h"
 #include "thermal_mg.h"
+#include "transient.h"
 
 #include <memory>
 
@@ -22,13 +23,17 @@ struct ThermalMgLevel {
 struct vfem_thermal_mg {
     ThermalMatrix K;
     const double *kappa;            // the caller's, read by every level-0 kernel
+    const double *cap = nullptr;    // vfem_transient_mg_create: the caller's element capacities, and level 0 is the two-term operator
+    ThermalCapacity mb{};           //   sum_e (kappa_e K + cap_e M(mb))
     const uint8_t *fixed_in;        // the caller's mask (may be null); the levels use their normalised copies
     std::vector<ThermalMgLevel> lv;
     CoarsestSolver coarsest;
     int N() const { return lv[0].g.N; }
     int L() const { return (int) lv.size() - 1; }
     size_t vec(int l) const { return (size_t) lv[l].g.nnode; }
-    ThermalLevelOp op(int l) const { return l == 0 ? ThermalLevelOp{nullptr, kappa, &K} : ThermalLevelOp{lv[l].A.p, nullptr, nullptr}; }
+    ThermalLevelOp op(int l) const {
+        return l == 0 ? ThermalLevelOp{nullptr, kappa, &K, cap, &mb} : ThermalLevelOp{lv[l].A.p, nullptr, nullptr, nullptr, nullptr};
+    }
     long long bytes() const {
         size_t d = 0, m = 0;
         for (const ThermalMgLevel &v : lv) {
@@ -46,7 +51,8 @@ void need_dinv0(vfem_thermal_mg *h, hipStream_t s) {
     ThermalMgLevel &v = h->lv[0];
     if (v.dinv.p) return;
     v.dinv.alloc((size_t) v.g.nnode);
-    launch_thermal_diagonal(v.g, h->K, h->kappa, v.fixed.p, 1, v.dinv.p, s);
+    if (h->cap) launch_transient_diagonal(v.g, h->K, h->mb, h->kappa, h->cap, v.fixed.p, 1, v.dinv.p, s);
+    else launch_thermal_diagonal(v.g, h->K, h->kappa, v.fixed.p, 1, v.dinv.p, s);
 }
 
 // one sweep over the 2^N colours of the level's nodes, ascending (forward) or descending
@@ -61,7 +67,8 @@ void sweep(vfem_thermal_mg *h, int l, double *x, const double *b, int forward, h
 
 void level_apply(vfem_thermal_mg *h, int l, const double *x, const double *b, double *out, hipStream_t s) {
     const ThermalMgLevel &v = h->lv[l];
-    if (l == 0) launch_thermal_apply(v.g, h->K, h->kappa, v.fixed.p, 1, x, b, out, s);
+    if (l == 0 && h->cap) launch_transient_apply(v.g, h->K, h->mb, h->kappa, h->cap, v.fixed.p, 1, 1, x, b, b ? 1 : 0, out, s);
+    else if (l == 0) launch_thermal_apply(v.g, h->K, h->kappa, v.fixed.p, 1, x, b, out, s);
     else launch_thermal_mg_apply(v.g, v.A.p, v.fixed.p, x, b, out, s);
 }
 
@@ -94,22 +101,23 @@ struct ThermalOps {
     }
 };
 
-}  // namespace
-
-extern "C" {
-
-int vfem_thermal_mg_create(vfem_thermal_mg **out, int dim, const int64_t *nelems_host, const double *Kc0_host, const double *kappa,
-                           const uint8_t *fixed, int max_coarsenings, void *stream) {
-    VFEM_TRY
-    const std::string w = "vfem_thermal_mg_create";
+// the body of both creates; two_term: level 0 takes mb_host [dim + 1] and cap beside Kc0_host and kappa
+void create(const std::string &w, vfem_thermal_mg **out, int dim, const int64_t *nelems_host, const double *Kc0_host, bool two_term,
+            const double *mb_host, const double *kappa, const double *cap, const uint8_t *fixed, int max_coarsenings, void *stream) {
     if (!out) throw Error(w + ": null argument");
     *out = nullptr;
     hipStream_t s = S(stream);
     ModalGrid g = grid_args(w, dim, nelems_host, nullptr, false);
     std::unique_ptr<vfem_thermal_mg> h(new vfem_thermal_mg);
     h->K = thermal_element_matrix(w, dim, Kc0_host);
-    if (!kappa) throw Error(w + ": null argument");
+    if (two_term) {
+        if (!mb_host) throw Error(w + ": null argument");
+        check_finite(w, "the capacity entries are", mb_host, dim + 1);
+        for (int d = 0; d <= dim; ++d) h->mb.m[d] = mb_host[d];
+    }
+    if (!kappa || (two_term && !cap)) throw Error(w + ": null argument");
     h->kappa = kappa;
+    h->cap = two_term ? cap : nullptr;
     h->fixed_in = fixed;
     const int N = g.N;
     // the levels (max_coarsenings < 0: as far as the extents allow); a coarser voxel has twice the edge lengths
@@ -165,12 +173,30 @@ int vfem_thermal_mg_create(vfem_thermal_mg **out, int dim, const int64_t *nelems
         h->coarsest.factor_dense(1, h->lv[L].fixed.p, s);
     } catch (const Error &e) {                  // a pivot that is not positive: what the PCG would report as its breakdown
         throw Error(w + ": breakdown at the coarsest level of the hierarchy " + sizes + ": " + e.what() +
-                    "; the operator is singular: no fixed node, a free node whose incident elements all have zero conductivity, or "
-                    "non-finite data");
+                    "; the operator is singular: " + (two_term ? "a free node whose incident elements all have zero conductivity and zero capacity"
+                                                               : "no fixed node, a free node whose incident elements all have zero conductivity") +
+                    ", or non-finite data");
     }
     VFEM_HIP(hipStreamSynchronize(s));          // the factorisation's workspace is not needed again
     h->coarsest.work = DenseWork();
     *out = h.release();
+}
+
+}  // namespace
+
+extern "C" {
+
+int vfem_thermal_mg_create(vfem_thermal_mg **out, int dim, const int64_t *nelems_host, const double *Kc0_host, const double *kappa,
+                           const uint8_t *fixed, int max_coarsenings, void *stream) {
+    VFEM_TRY
+    create("vfem_thermal_mg_create", out, dim, nelems_host, Kc0_host, false, nullptr, kappa, nullptr, fixed, max_coarsenings, stream);
+    VFEM_CATCH
+}
+
+int vfem_transient_mg_create(vfem_thermal_mg **out, int dim, const int64_t *nelems_host, const double *Ka_host, const double *mb_host,
+                             const double *kappa, const double *cap, const uint8_t *fixed, int max_coarsenings, void *stream) {
+    VFEM_TRY
+    create("vfem_transient_mg_create", out, dim, nelems_host, Ka_host, true, mb_host, kappa, cap, fixed, max_coarsenings, stream);
     VFEM_CATCH
 }
 
@@ -265,7 +291,10 @@ int vfem_thermal_mg_pcg(vfem_thermal_mg *h, const double *b, double *x, double t
     if (overlaps(x, g.nnode, b, g.nnode)) throw Error(w + ": x aliases b");
     // z = V-cycle(r); the host looks after every iteration, so the count is exact: a look costs little beside a cycle
     const ThermalPreconditioner multigrid = [&](const double *r, double *z) { cycle_from_zero<ThermalOps>(h, r, z, smoothing, s); };
-    thermal_pcg(w, g, h->K, h->kappa, h->lv[0].fixed.p, b, x, tol, max_iter, 1, multigrid, iterations_out_host, relres_out_host, s);
+    const ThermalApply apply = [&](const double *v, const double *rhs, double *res) { level_apply(h, 0, v, rhs, res, s); };
+    thermal_pcg(w, g.nnode, apply, h->cap ? "a free node whose incident elements all have zero conductivity and zero capacity"
+                                          : "no fixed node, a free node whose incident elements all have zero conductivity",
+                b, x, tol, max_iter, 1, multigrid, iterations_out_host, relres_out_host, s);
     VFEM_CATCH
 }
 

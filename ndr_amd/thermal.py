@@ -85,6 +85,7 @@ class HeatConductionSimulator:
         if lo.size != ne.size or hi.size != ne.size or not np.all(hi > lo) or not (np.isfinite(lo).all() and np.isfinite(hi).all()):
             raise RuntimeError("HeatConductionSimulator: the bounding box must have %d finite coordinates per corner, upper > lower" % ne.size)
         self.N = int(ne.size)
+        self._version = 0                   # counts the changes of the operator (what ndr_amd.transient keeps its own factor by)
         self._ne, self._nn = ne, ne + 1
         self._bbmin, self._bbmax = lo, hi
         self._h = (hi - lo) / ne
@@ -123,6 +124,7 @@ class HeatConductionSimulator:
     def _changed(self):
         """the operator changed: the kept factor and the kept hierarchy no longer stand for it"""
         self._band = None
+        self._version += 1
         self._drop_multigrid()
 
     def _drop_multigrid(self):
