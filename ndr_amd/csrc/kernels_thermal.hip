@@ -1,15 +1,17 @@
-// Steady heat conduction on a degree-1 grid (thermal.h): the scalar operator A = P (sum_e kappa_e Kc0) P + (I - P) on a
-// block of nodal fields, its diagonal, the load of a volumetric source, the band of A for the direct solver, the density gradient
-// of a sum of bilinear forms and the centre flux.
+// Heat conduction on a degree-1 grid (thermal.h): the scalar operator
+// A = P (sum_e kappa_e K + sum_e cap_e M(mb)) P + iota (I - P) on a block of nodal fields, its diagonal and its band for the direct
+// solver, each kernel instantiated for the one-term form of the steady problem (no capacity term, iota = 1) and for the two-term form
+// of a transient step; the load of a volumetric source, the density gradient of a sum of bilinear forms and the centre flux.
 //
 // All of them stream fp64 and do little arithmetic per byte.  Every sum has a fixed order and no kernel uses an atomic: the same
-// bits run to run.  Device pointers need 8-byte alignment only (every access is one double).  Kc0 (at most 64 doubles) travels in
-// the kernel arguments: unrolled code reads it by uniform loads, the band kernel indexes it per lane.
+// bits run to run.  Device pointers need 8-byte alignment only (every access is one double).  K (at most 64 doubles) and mb (4
+// doubles) travel in the kernel arguments: unrolled code reads them by uniform loads, the band kernel indexes them per lane.
 //
 // Apply: one thread per NODE (cell_threads.h), all columns: k_modal_mass_apply's form.  The coupling of the pair (node, node + o) is
 // the sum over the elements that hold both of kappa[e] Kc0[el][j], el the node's local index there and j the neighbour's.  The
 // thread forms these 3^N coefficients once from its 2^N conductivities (elements in ascending el, j ascending within) and then
-// walks the columns: 3^N loads of X and one store per column.  A fixed node copies its own value; a fixed neighbour is skipped.
+// walks the columns: 3^N loads of X and one store per column.  A fixed node gives iota times its own value; a fixed neighbour is
+// skipped.  The two-term form adds cap[e] M[el][j] to every coupling, the conduction term first.
 // (A branch-free column loop -- coefficient 0 and offset 0 for a neighbour that takes no part, all 3^N loads issued together -- was
 // tried and measured: 132 VGPRs and 3 waves per SIMD in 3-D, one column 0.71 ms against 0.47 ms on 256 x 256 x 128, eight columns 1.91
 // against 2.23 ms.  The solver applies one column, so the predicated form stays)
@@ -24,17 +26,21 @@ namespace vfem {
 namespace {
 
 // (the node's couplings and the neighbours that take part: thermal_device.h, shared with the multigrid kernels; expanded here as
-// macros, which keeps this kernel's registers where they were)
-template <int N>
-__global__ void __launch_bounds__(256) k_thermal_apply(ModalGrid g, ThermalMatrix K, const double *__restrict__ kappa,
-                                                       const uint8_t *__restrict__ fixed, int ncols, const double *__restrict__ X,
-                                                       const double *__restrict__ b, double *__restrict__ Y) {
+// macros, and the body of both forms here and not in a shared function, which keeps this kernel's registers where they were.
+// TWO: the two-term form; the one-term form has iota = 1 and b for a residual as compile-time facts)
+template <int N, bool TWO>
+__global__ void __launch_bounds__(256) k_thermal_apply(ModalGrid g, ThermalMatrix K, OnlyTwoTerm<TWO, ThermalCapacity> mb,
+                                                       const double *__restrict__ kappa,
+                                                       OnlyTwoTerm<TWO, const double *__restrict__> cap,
+                                                       const uint8_t *__restrict__ fixed, OnlyTwoTerm<TWO, int> identity, int ncols,
+                                                       const double *__restrict__ X, const double *__restrict__ b,
+                                                       OnlyTwoTerm<TWO, int> residual, double *__restrict__ Y) {
     constexpr int NB = ThermalTraits<N>::NB, SELF = ThermalTraits<N>::SELF;
     int c[N];
     if (!thread_cell<N>(g.ne, 1, c)) return;
     const long long node = flat_index<N>(g.ne, 1, c);
     double coef[NB];
-    VFEM_THERMAL_COUPLINGS(N, g, K, kappa, c, coef);
+    VFEM_THERMAL_COUPLINGS(N, TWO, g, K, mb, kappa, cap, c, coef);
     long long delta[NB];            // the neighbour's node index minus this one's
     unsigned live = 0u;             // neighbours inside the grid that are not fixed
     VFEM_THERMAL_LIVE_NEIGHBOURS(N, g, fixed, c, node, delta, live);
@@ -42,18 +48,28 @@ __global__ void __launch_bounds__(256) k_thermal_apply(ModalGrid g, ThermalMatri
     for (int col = 0; col < ncols; ++col) {
         const double *__restrict__ x = X + col * g.nnode + node;
         double acc = 0.0;
-        if (self_fixed) acc = x[0];
-        else {
+        if (self_fixed) {
+            if constexpr (TWO) acc = identity ? x[0] : 0.0;
+            else acc = x[0];
+        } else {
 #pragma unroll
             for (int k = 0; k < NB; ++k)
                 if ((live >> k) & 1u) acc = fma(coef[k], x[delta[k]], acc);
         }
-        Y[col * g.nnode + node] = b ? b[col * g.nnode + node] - acc : acc;
+        if constexpr (TWO) {
+            if (b) {
+                const double bv = b[col * g.nnode + node];
+                acc = residual ? bv - acc : (self_fixed ? acc : acc + bv);
+            }
+            Y[col * g.nnode + node] = acc;
+        } else Y[col * g.nnode + node] = b ? b[col * g.nnode + node] - acc : acc;
     }
 }
 
-template <int N>
-__global__ void __launch_bounds__(256) k_thermal_diagonal(ModalGrid g, ThermalMatrix K, const double *__restrict__ kappa,
+template <int N, bool TWO>
+__global__ void __launch_bounds__(256) k_thermal_diagonal(ModalGrid g, ThermalMatrix K, OnlyTwoTerm<TWO, ThermalCapacity> mb,
+                                                          const double *__restrict__ kappa,
+                                                          OnlyTwoTerm<TWO, const double *__restrict__> cap,
                                                           const uint8_t *__restrict__ fixed, int invert, double *__restrict__ out) {
     constexpr int NPE = ThermalTraits<N>::NPE;
     int c[N];
@@ -61,7 +77,10 @@ __global__ void __launch_bounds__(256) k_thermal_diagonal(ModalGrid g, ThermalMa
     const long long node = flat_index<N>(g.ne, 1, c);
     double d = 0.0;
 #pragma unroll
-    for (int el = 0; el < NPE; ++el) d = fma(incident_kappa<N>(g, kappa, c, el), K.k[el * NPE + el], d);
+    for (int el = 0; el < NPE; ++el) {
+        d = fma(incident_kappa<N>(g, kappa, c, el), K.k[el * NPE + el], d);
+        if constexpr (TWO) d = fma(incident_kappa<N>(g, cap, c, el), mb.m[0], d);
+    }
     if (fixed && fixed[node]) d = 1.0;
     out[node] = invert ? 1.0 / d : d;
 }
@@ -84,10 +103,11 @@ __global__ void __launch_bounds__(256) k_thermal_source(ModalGrid g, double shar
 constexpr long long TILE = 64 * 64;
 
 // one thread per stored entry of the nb (bt + 1) tiles, as k_band_assemble (band_spd.hip) has it for the stiffness matrix
-template <int N>
-__global__ void __launch_bounds__(256) k_thermal_band(ModalGrid g, ThermalMatrix K, long long n, long long w, long long nb, int bt,
-                                                      const double *__restrict__ kappa, const uint8_t *__restrict__ fixed,
-                                                      double *__restrict__ band) {
+template <int N, bool TWO>
+__global__ void __launch_bounds__(256) k_thermal_band(ModalGrid g, ThermalMatrix K, OnlyTwoTerm<TWO, ThermalCapacity> mb, long long n,
+                                                      long long w, long long nb, int bt, const double *__restrict__ kappa,
+                                                      OnlyTwoTerm<TWO, const double *__restrict__> cap,
+                                                      const uint8_t *__restrict__ fixed, double *__restrict__ band) {
     constexpr int NPE = ThermalTraits<N>::NPE;
     const long long per_row = (long long) (bt + 1) * TILE;
     for (long long t = (long long) blockIdx.x * 256 + threadIdx.x; t < nb * per_row; t += (long long) gridDim.x * 256) {
@@ -126,6 +146,7 @@ __global__ void __launch_bounds__(256) k_thermal_band(ModalGrid g, ThermalMatrix
                                     lj = 2 * lj + xj[ax] - ee[ax];
                                 }
                                 v = fma(kappa[el], K.k[li * NPE + lj], v);
+                                if constexpr (TWO) v = fma(cap[el], mb.m[__popc(li ^ lj)], v);
                             }
             }
         }
@@ -225,20 +246,28 @@ unsigned blocks_for(long long n) { return (unsigned) std::max<long long>(1, std:
 
 }  // namespace
 
-void launch_thermal_apply(const ModalGrid &g, const ThermalMatrix &K, const double *kappa, const uint8_t *fixed, int ncols,
-                          const double *X, const double *b, double *Y, hipStream_t s) {
+// `kernel` (a template of N and TWO) in the instantiation for the grid's N; each launcher below has one such line per form, with
+// NoCapacity{} where the one-term instantiation has its placeholders
+#define THERMAL_LAUNCH(kernel, TWO, N_, ...) \
+    do { if ((N_) == 3) kernel<3, TWO> __VA_ARGS__; else kernel<2, TWO> __VA_ARGS__; VFEM_HIP(hipGetLastError()); } while (0)
+
+void launch_thermal_apply(const ModalGrid &g, const ThermalOp &op, const uint8_t *fixed, int identity, int ncols, const double *X,
+                          const double *b, int residual, double *Y, hipStream_t s) {
     const dim3 grd = cell_grid(g.N, g.ne, 1);
-    if (g.N == 3) k_thermal_apply<3><<<grd, cell_block(), 0, s>>>(g, K, kappa, fixed, ncols, X, b, Y);
-    else k_thermal_apply<2><<<grd, cell_block(), 0, s>>>(g, K, kappa, fixed, ncols, X, b, Y);
-    VFEM_HIP(hipGetLastError());
+    const NoCapacity none;
+    if (op.cap)
+        THERMAL_LAUNCH(k_thermal_apply, true, g.N, <<<grd, cell_block(), 0, s>>>(g, op.K, op.mb, op.kappa, op.cap, fixed, identity, ncols, X, b, residual, Y));
+    else {
+        if (!identity || (b && !residual)) throw Error("launch_thermal_apply: the one-term form has iota = 1 and takes b for a residual");
+        THERMAL_LAUNCH(k_thermal_apply, false, g.N, <<<grd, cell_block(), 0, s>>>(g, op.K, none, op.kappa, none, fixed, none, ncols, X, b, none, Y));
+    }
 }
 
-void launch_thermal_diagonal(const ModalGrid &g, const ThermalMatrix &K, const double *kappa, const uint8_t *fixed, int invert,
-                             double *d, hipStream_t s) {
+void launch_thermal_diagonal(const ModalGrid &g, const ThermalOp &op, const uint8_t *fixed, int invert, double *d, hipStream_t s) {
     const dim3 grd = cell_grid(g.N, g.ne, 1);
-    if (g.N == 3) k_thermal_diagonal<3><<<grd, cell_block(), 0, s>>>(g, K, kappa, fixed, invert, d);
-    else k_thermal_diagonal<2><<<grd, cell_block(), 0, s>>>(g, K, kappa, fixed, invert, d);
-    VFEM_HIP(hipGetLastError());
+    const NoCapacity none;
+    if (op.cap) THERMAL_LAUNCH(k_thermal_diagonal, true, g.N, <<<grd, cell_block(), 0, s>>>(g, op.K, op.mb, op.kappa, op.cap, fixed, invert, d));
+    else THERMAL_LAUNCH(k_thermal_diagonal, false, g.N, <<<grd, cell_block(), 0, s>>>(g, op.K, none, op.kappa, none, fixed, invert, d));
 }
 
 void launch_thermal_source(const ModalGrid &g, const double *q, const uint8_t *fixed, const double *f_in, double *f_out,
@@ -252,16 +281,15 @@ void launch_thermal_source(const ModalGrid &g, const double *q, const uint8_t *f
     VFEM_HIP(hipGetLastError());
 }
 
-void launch_thermal_band_assemble(const ModalGrid &g, const ThermalMatrix &K, const double *kappa, const uint8_t *fixed, double *band,
-                                  hipStream_t s) {
+void launch_thermal_band_assemble(const ModalGrid &g, const ThermalOp &op, const uint8_t *fixed, double *band, hipStream_t s) {
     long long n, w;
     thermal_band_geometry(g, n, w);
     const long long nb = (n + 63) / 64;
     const int bt = (int) ((w + 63) / 64);
     const unsigned blocks = blocks_for(nb * (bt + 1) * TILE);
-    if (g.N == 3) k_thermal_band<3><<<blocks, 256, 0, s>>>(g, K, n, w, nb, bt, kappa, fixed, band);
-    else k_thermal_band<2><<<blocks, 256, 0, s>>>(g, K, n, w, nb, bt, kappa, fixed, band);
-    VFEM_HIP(hipGetLastError());
+    const NoCapacity none;
+    if (op.cap) THERMAL_LAUNCH(k_thermal_band, true, g.N, <<<blocks, 256, 0, s>>>(g, op.K, op.mb, n, w, nb, bt, op.kappa, op.cap, fixed, band));
+    else THERMAL_LAUNCH(k_thermal_band, false, g.N, <<<blocks, 256, 0, s>>>(g, op.K, none, n, w, nb, bt, op.kappa, none, fixed, band));
 }
 
 void launch_thermal_gradient(const ModalGrid &g, const ThermalMatrix &K, int ncols, const ThermalCoef &c, const double *dkappa,

@@ -4,9 +4,9 @@
 //
 // All fp64, one double per access (8-byte alignment is enough), no atomics: one thread owns what it writes and sums in a fixed order,
 // so two runs give the same bits.  A level's couplings come from a source: ThermalFineSrc forms them from the node's 2^N
-// conductivities as k_thermal_apply does (thermal_couplings, thermal_device.h), ThermalTwoTermSrc adds the capacity term of a
-// transient step's operator in separate instantiations, ThermalStoredSrc loads A[offset][node] (coalesced over the
-// nodes of a wave).  Both give the 3^N coefficients, the neighbour distances and the bits of the neighbours that take part.
+// conductivities as k_thermal_apply does (thermal_couplings, thermal_device.h), with the capacity term of a transient step's
+// operator in instantiations of their own, ThermalStoredSrc loads A[offset][node] (coalesced over the nodes of a
+// wave).  Both give the 3^N coefficients, the neighbour distances and the bits of the neighbours that take part.
 //
 // Level-0 colour sweep (the hot path: two sweeps of 2^N colours per cycle over all fine nodes): one thread per node of the colour,
 // 64 x 4 blocks over the colour's sub-grid with the lanes along the last axis.  The lanes of a wave touch every second double of a
@@ -25,25 +25,17 @@ namespace {
 
 constexpr int MG_T = 256;
 
+// level 0: Extra is NoCapacity, or the CapacityTerm of a transient step's hierarchy (thermal_device.h).  The empty member takes no
+// room and the full one sits behind K: the layouts the two forms had as separate types, and with them their code
+template <class Extra>
 struct ThermalFineSrc {
     ThermalMatrix K;
+    [[no_unique_address]] Extra extra;
     const double *kappa;
     template <int N>
     __device__ __forceinline__ void couplings(const ModalGrid &g, const int (&c)[N], long long node,
                                               double (&coef)[ThermalTraits<N>::NB]) const {
-        thermal_couplings<N>(g, K, kappa, c, coef);
-    }
-};
-
-// level 0 of a transient step's hierarchy: both terms (transient_couplings, thermal_device.h)
-struct ThermalTwoTermSrc {
-    ThermalMatrix K;
-    ThermalCapacity mb;
-    const double *kappa, *cap;
-    template <int N>
-    __device__ __forceinline__ void couplings(const ModalGrid &g, const int (&c)[N], long long node,
-                                              double (&coef)[ThermalTraits<N>::NB]) const {
-        transient_couplings<N>(g, K, mb, kappa, cap, c, coef);
+        thermal_couplings<N>(g, K, kappa, extra, c, coef);
     }
 };
 
@@ -309,6 +301,14 @@ unsigned blocks_for(long long n) { return (unsigned) std::max<long long>(1, (n +
 
 #define THERMAL_MG_DISPATCH(g, call2, call3) do { if ((g).N == 2) { call2; } else { call3; } VFEM_HIP(hipGetLastError()); } while (0)
 
+// launch(src) with the source object of a level's operator: the stored stencil, or level 0 in its one-term or two-term form
+template <class Launch>
+void with_source(const ThermalLevelOp &op, const Launch &launch) {
+    if (!op.fine) launch(ThermalStoredSrc{op.A});
+    else if (op.fine->cap) launch(ThermalFineSrc<CapacityTerm>{op.fine->K, {op.fine->mb, op.fine->cap}, op.fine->kappa});
+    else launch(ThermalFineSrc<NoCapacity>{op.fine->K, {}, op.fine->kappa});
+}
+
 void launch_thermal_mg_normalise_mask(long long n, const uint8_t *in, uint8_t *out, hipStream_t s) {
     k_thermal_mg_normalise_mask<<<blocks_for(n), MG_T, 0, s>>>(n, in, out);
     VFEM_HIP(hipGetLastError());
@@ -324,18 +324,12 @@ void launch_thermal_mg_galerkin(const ModalGrid &fine, const ModalGrid &coarse, 
                                 const uint8_t *fixed_c, double *Ac, hipStream_t s) {
     const GsColor all = all_nodes(coarse);
     const dim3 grd(flat_blocks(all), fine.N == 2 ? 9 : 27);
-#define ARGS(SRC) <<<grd, MG_T, 0, s>>>(fine, coarse, SRC, all, fixed_f, fixed_c, Ac)
-    if (src.cap) {
-        const ThermalTwoTermSrc f{*src.K, *src.mb, src.kappa, src.cap};
-        THERMAL_MG_DISPATCH(fine, (k_thermal_mg_galerkin<2, ThermalTwoTermSrc> ARGS(f)), (k_thermal_mg_galerkin<3, ThermalTwoTermSrc> ARGS(f)));
-    } else if (src.kappa) {
-        const ThermalFineSrc f{*src.K, src.kappa};
-        THERMAL_MG_DISPATCH(fine, (k_thermal_mg_galerkin<2, ThermalFineSrc> ARGS(f)), (k_thermal_mg_galerkin<3, ThermalFineSrc> ARGS(f)));
-    } else {
-        const ThermalStoredSrc f{src.A};
-        THERMAL_MG_DISPATCH(fine, (k_thermal_mg_galerkin<2, ThermalStoredSrc> ARGS(f)), (k_thermal_mg_galerkin<3, ThermalStoredSrc> ARGS(f)));
-    }
+    with_source(src, [&](auto f) {
+        using Src = decltype(f);
+#define ARGS <<<grd, MG_T, 0, s>>>(fine, coarse, f, all, fixed_f, fixed_c, Ac)
+        THERMAL_MG_DISPATCH(fine, (k_thermal_mg_galerkin<2, Src> ARGS), (k_thermal_mg_galerkin<3, Src> ARGS));
 #undef ARGS
+    });
 }
 
 void launch_thermal_mg_dinv(const ModalGrid &g, const double *A, const uint8_t *fixed, double *dinv, hipStream_t s) {
@@ -355,24 +349,15 @@ void launch_thermal_mg_apply(const ModalGrid &g, const double *A, const uint8_t 
 
 void launch_thermal_mg_sweep_colour(const ModalGrid &g, const ThermalLevelOp &src, const uint8_t *fixed, const double *dinv,
                                     const GsColor &colour, double *x, const double *b, hipStream_t s) {
-    if (src.cap) {
-        const ThermalTwoTermSrc f{*src.K, *src.mb, src.kappa, src.cap};
-        const dim3 grd = cell_blocks(g.N, colour);
-#define ARGS <<<grd, cell_block(), 0, s>>>(g, f, fixed, dinv, colour, x, b, x)
-        THERMAL_MG_DISPATCH(g, (k_thermal_mg_level<2, MG_SWEEP, ThermalTwoTermSrc, true> ARGS), (k_thermal_mg_level<3, MG_SWEEP, ThermalTwoTermSrc, true> ARGS));
+    // level 0 takes the 64 x 4 blocks of the cell kernels, a stored level flat ones: its rows are short
+    with_source(src, [&](auto f) {
+        using Src = decltype(f);
+        constexpr bool CELL = !std::is_same<Src, ThermalStoredSrc>::value;
+        const dim3 grd = CELL ? cell_blocks(g.N, colour) : dim3(flat_blocks(colour)), blk = CELL ? cell_block() : dim3(MG_T);
+#define ARGS <<<grd, blk, 0, s>>>(g, f, fixed, dinv, colour, x, b, x)
+        THERMAL_MG_DISPATCH(g, (k_thermal_mg_level<2, MG_SWEEP, Src, CELL> ARGS), (k_thermal_mg_level<3, MG_SWEEP, Src, CELL> ARGS));
 #undef ARGS
-    } else if (src.kappa) {
-        const ThermalFineSrc f{*src.K, src.kappa};
-        const dim3 grd = cell_blocks(g.N, colour);
-#define ARGS <<<grd, cell_block(), 0, s>>>(g, f, fixed, dinv, colour, x, b, x)
-        THERMAL_MG_DISPATCH(g, (k_thermal_mg_level<2, MG_SWEEP, ThermalFineSrc, true> ARGS), (k_thermal_mg_level<3, MG_SWEEP, ThermalFineSrc, true> ARGS));
-#undef ARGS
-    } else {
-        const ThermalStoredSrc f{src.A};
-#define ARGS <<<flat_blocks(colour), MG_T, 0, s>>>(g, f, fixed, dinv, colour, x, b, x)
-        THERMAL_MG_DISPATCH(g, (k_thermal_mg_level<2, MG_SWEEP, ThermalStoredSrc, false> ARGS), (k_thermal_mg_level<3, MG_SWEEP, ThermalStoredSrc, false> ARGS));
-#undef ARGS
-    }
+    });
 }
 
 void launch_thermal_mg_restrict(const ModalGrid &fine, const ModalGrid &coarse, const uint8_t *fixed_f, const uint8_t *fixed_c,
@@ -393,18 +378,12 @@ void launch_thermal_mg_prolong_add(const ModalGrid &fine, const ModalGrid &coars
 
 void launch_thermal_mg_dense(const ModalGrid &g, const ThermalLevelOp &src, const uint8_t *fixed, double *M, hipStream_t s) {
     const GsColor all = all_nodes(g);
-#define ARGS(SRC) <<<flat_blocks(all), MG_T, 0, s>>>(g, SRC, all, fixed, M)
-    if (src.cap) {
-        const ThermalTwoTermSrc f{*src.K, *src.mb, src.kappa, src.cap};
-        THERMAL_MG_DISPATCH(g, (k_thermal_mg_dense<2, ThermalTwoTermSrc> ARGS(f)), (k_thermal_mg_dense<3, ThermalTwoTermSrc> ARGS(f)));
-    } else if (src.kappa) {
-        const ThermalFineSrc f{*src.K, src.kappa};
-        THERMAL_MG_DISPATCH(g, (k_thermal_mg_dense<2, ThermalFineSrc> ARGS(f)), (k_thermal_mg_dense<3, ThermalFineSrc> ARGS(f)));
-    } else {
-        const ThermalStoredSrc f{src.A};
-        THERMAL_MG_DISPATCH(g, (k_thermal_mg_dense<2, ThermalStoredSrc> ARGS(f)), (k_thermal_mg_dense<3, ThermalStoredSrc> ARGS(f)));
-    }
+    with_source(src, [&](auto f) {
+        using Src = decltype(f);
+#define ARGS <<<flat_blocks(all), MG_T, 0, s>>>(g, f, all, fixed, M)
+        THERMAL_MG_DISPATCH(g, (k_thermal_mg_dense<2, Src> ARGS), (k_thermal_mg_dense<3, Src> ARGS));
 #undef ARGS
+    });
 }
 
 void launch_thermal_mg_copy_fixed(long long n, const uint8_t *fixed, const double *b, double *x, hipStream_t s) {

@@ -1,6 +1,8 @@
-// The heat-conduction entry points of include/vfem.h (vfem_thermal_*).  Handle-free: every call takes the grid, and
-// the element matrix or the voxel's edge lengths where its kernel needs them.  Every argument is checked before the first device
-// call.
+// The heat-conduction entry points of include/vfem.h that take the operator: the steady ones (vfem_thermal_*)
+// and their two-term twins of a transient step (vfem_transient_{apply, diagonal, band_assemble, pcg}), which are wrappers over one
+// body each.  Handle-free: every call takes the grid, and the element matrix or the voxel's edge lengths where its kernel needs
+// them; the transient calls take the capacity entries and the element capacities too, with the scalars of the time scheme folded in
+// by the caller.  Every argument is checked before the first device call.
 #include "grid_args.h"
 #include "thermal.h"
 #include "vfem_host.h"
@@ -13,10 +15,68 @@ namespace {
 
 constexpr int THERMAL_PCG_CHECK = 8;        // the host looks at the residual once every so many iterations, as the cell problems do
 
-// an output of `len` doubles against the element multipliers and the fixed-node bytes (either may be null)
-void check_thermal_output(const std::string &w, const char *name, const ModalGrid &g, const double *out, int64_t len, const double *kappa,
-                          const uint8_t *fixed) {
-    check_output(w, name, out, len, g, kappa, "the element multipliers", fixed, "the fixed-node mask");
+// an output of `len` doubles against the operator's element fields and the fixed-node bytes (may be null)
+void check_operator_output(const std::string &w, const char *name, const ModalGrid &g, const double *out, int64_t len, const ThermalOp &op,
+                           const uint8_t *fixed) {
+    check_output(w, name, out, len, g, op.kappa, op.cap ? "the element conductivities" : "the element multipliers", fixed, "the fixed-node mask");
+    if (op.cap) check_output(w, name, out, len, g, op.cap, "the element capacities", nullptr, "");
+}
+
+// The bodies of the paired entry points; two_term: the call takes mb_host [dim + 1] and cap beside K_host and kappa
+
+void apply_entry(const std::string &w, int dim, const int64_t *nelems_host, const double *K_host, bool two_term, const double *mb_host,
+                 const double *kappa, const double *cap, const uint8_t *fixed, int identity, int ncols, const double *X, const double *b,
+                 double *Y, void *stream) {
+    const ModalGrid g = grid_args(w, dim, nelems_host, nullptr, false);
+    const ThermalOp op = thermal_operator_args(w, dim, K_host, two_term, mb_host, kappa, cap);
+    if (!X || !Y) throw Error(w + ": null argument");
+    if (identity != 0 && identity != 1) throw Error(w + ": identity must be 0 or 1");
+    check_count(w, "ncols", ncols, THERMAL_MAX_COLS);
+    const int64_t len = (int64_t) ncols * g.nnode;
+    if (overlaps(Y, len, X, len)) throw Error(w + ": Y aliases X");
+    if (b && overlaps(Y, len, b, len)) throw Error(w + ": Y aliases b");
+    check_operator_output(w, "Y", g, Y, len, op, fixed);
+    launch_thermal_apply(g, op, fixed, identity, ncols, X, b, 0, Y, S(stream));
+}
+
+void diagonal_entry(const std::string &w, int dim, const int64_t *nelems_host, const double *K_host, bool two_term, const double *mb_host,
+                    const double *kappa, const double *cap, const uint8_t *fixed, double *diag, void *stream) {
+    const ModalGrid g = grid_args(w, dim, nelems_host, nullptr, false);
+    const ThermalOp op = thermal_operator_args(w, dim, K_host, two_term, mb_host, kappa, cap);
+    if (!diag) throw Error(w + ": null argument");
+    check_operator_output(w, "diag", g, diag, g.nnode, op, fixed);
+    launch_thermal_diagonal(g, op, fixed, 0, diag, S(stream));
+}
+
+void band_entry(const std::string &w, int dim, const int64_t *nelems_host, const double *K_host, bool two_term, const double *mb_host,
+                const double *kappa, const double *cap, const uint8_t *fixed, double *band, void *stream) {
+    const ModalGrid g = grid_args(w, dim, nelems_host, nullptr, false);
+    const ThermalOp op = thermal_operator_args(w, dim, K_host, two_term, mb_host, kappa, cap);
+    if (!band) throw Error(w + ": null argument");
+    long long n, hw;
+    thermal_band_geometry(g, n, hw);
+    check_operator_output(w, "band", g, band, band_spd_doubles(n, hw), op, fixed);
+    launch_thermal_band_assemble(g, op, fixed, band, S(stream));
+}
+
+void pcg_entry(const std::string &w, int dim, const int64_t *nelems_host, const double *K_host, bool two_term, const double *mb_host,
+               const double *kappa, const double *cap, const uint8_t *fixed, const double *b, double *x, double tol, int max_iter,
+               int *iterations_out_host, double *relres_out_host, void *stream) {
+    hipStream_t s = S(stream);
+    const ModalGrid g = grid_args(w, dim, nelems_host, nullptr, false);
+    const ThermalOp op = thermal_operator_args(w, dim, K_host, two_term, mb_host, kappa, cap);
+    if (!b || !x || !iterations_out_host || !relres_out_host) throw Error(w + ": null argument");
+    if (!(tol > 0.0) || !std::isfinite(tol) || max_iter < 1) throw Error(w + ": tol must be positive and max_iter at least 1");
+    const long long n = g.nnode;
+    if (overlaps(x, n, b, n)) throw Error(w + ": x aliases b");
+    check_operator_output(w, "x", g, x, n, op, fixed);
+    DevBuf<double> dinv;
+    dinv.alloc((size_t) n);
+    launch_thermal_diagonal(g, op, fixed, 1, dinv.p, s);
+    const ThermalPreconditioner jacobi = [&](const double *r, double *z) { launch_thermal_scale(n, dinv.p, r, z, s); };
+    const ThermalApply apply = [&](const double *v, const double *rhs, double *out) { launch_thermal_apply(g, op, fixed, 1, 1, v, rhs, 1, out, s); };
+    thermal_pcg(w, n, apply, thermal_singular_because(op), b, x, tol, max_iter, THERMAL_PCG_CHECK, jacobi, iterations_out_host,
+                relres_out_host, s);
 }
 
 }  // namespace
@@ -30,6 +90,25 @@ ThermalMatrix thermal_element_matrix(const std::string &w, int dim, const double
     ThermalMatrix K{};
     for (int i = 0; i < npe * npe; ++i) K.k[i] = Kc0[i];
     return K;
+}
+
+ThermalCapacity thermal_capacity_entries(const std::string &w, int dim, const double *m_host) {
+    if (!m_host) throw Error(w + ": null argument");
+    check_finite(w, "the capacity entries are", m_host, dim + 1);
+    ThermalCapacity m{};
+    for (int d = 0; d <= dim; ++d) m.m[d] = m_host[d];
+    return m;
+}
+
+ThermalOp thermal_operator_args(const std::string &w, int dim, const double *K_host, bool two_term, const double *mb_host,
+                                const double *kappa, const double *cap) {
+    ThermalOp op{};
+    op.K = thermal_element_matrix(w, dim, K_host);
+    if (two_term) op.mb = thermal_capacity_entries(w, dim, mb_host);
+    if (!kappa || (two_term && !cap)) throw Error(w + ": null argument");
+    op.kappa = kappa;
+    op.cap = two_term ? cap : nullptr;
+    return op;
 }
 
 void thermal_pcg(const std::string &w, long long n, const ThermalApply &apply, const char *singular_because, const double *b, double *x,
@@ -97,14 +176,6 @@ void thermal_pcg(const std::string &w, long long n, const ThermalApply &apply, c
     }
 }
 
-void thermal_pcg(const std::string &w, const ModalGrid &g, const ThermalMatrix &K, const double *kappa, const uint8_t *fixed,
-                 const double *b, double *x, double tol, int max_iter, int look_every, const ThermalPreconditioner &precondition,
-                 int *iterations_out_host, double *relres_out_host, hipStream_t s) {
-    const ThermalApply apply = [&](const double *v, const double *rhs, double *out) { launch_thermal_apply(g, K, kappa, fixed, 1, v, rhs, out, s); };
-    thermal_pcg(w, g.nnode, apply, "no fixed node, a free node whose incident elements all have zero conductivity", b, x, tol, max_iter,
-                look_every, precondition, iterations_out_host, relres_out_host, s);
-}
-
 }  // namespace vfem
 
 extern "C" {
@@ -112,27 +183,14 @@ extern "C" {
 int vfem_thermal_apply(int dim, const int64_t *nelems_host, const double *Kc0_host, const double *kappa, const uint8_t *fixed,
                        int ncols, const double *X, double *Y, void *stream) {
     VFEM_TRY
-    const std::string w = "vfem_thermal_apply";
-    const ModalGrid g = grid_args(w, dim, nelems_host, nullptr, false);
-    const ThermalMatrix K = thermal_element_matrix(w, dim, Kc0_host);
-    if (!kappa || !X || !Y) throw Error(w + ": null argument");
-    check_count(w, "ncols", ncols, THERMAL_MAX_COLS);
-    const int64_t len = (int64_t) ncols * g.nnode;
-    if (overlaps(Y, len, X, len)) throw Error(w + ": Y aliases X");
-    check_thermal_output(w, "Y", g, Y, len, kappa, fixed);
-    launch_thermal_apply(g, K, kappa, fixed, ncols, X, nullptr, Y, S(stream));
+    apply_entry("vfem_thermal_apply", dim, nelems_host, Kc0_host, false, nullptr, kappa, nullptr, fixed, 1, ncols, X, nullptr, Y, stream);
     VFEM_CATCH
 }
 
 int vfem_thermal_diagonal(int dim, const int64_t *nelems_host, const double *Kc0_host, const double *kappa, const uint8_t *fixed,
                           double *diag, void *stream) {
     VFEM_TRY
-    const std::string w = "vfem_thermal_diagonal";
-    const ModalGrid g = grid_args(w, dim, nelems_host, nullptr, false);
-    const ThermalMatrix K = thermal_element_matrix(w, dim, Kc0_host);
-    if (!kappa || !diag) throw Error(w + ": null argument");
-    check_thermal_output(w, "diag", g, diag, g.nnode, kappa, fixed);
-    launch_thermal_diagonal(g, K, kappa, fixed, 0, diag, S(stream));
+    diagonal_entry("vfem_thermal_diagonal", dim, nelems_host, Kc0_host, false, nullptr, kappa, nullptr, fixed, diag, stream);
     VFEM_CATCH
 }
 
@@ -145,7 +203,7 @@ int vfem_thermal_source(int dim, const int64_t *nelems_host, const double *h_hos
     if (!f_out) throw Error(w + ": null argument");
     if (!q && !f_in) throw Error(w + ": null argument: neither a volumetric nor a nodal source");
     if (f_in && f_in != f_out && overlaps(f_out, g.nnode, f_in, g.nnode)) throw Error(w + ": f_out overlaps f_in without being f_in");
-    check_thermal_output(w, "f_out", g, f_out, g.nnode, q, fixed);
+    check_output(w, "f_out", f_out, g.nnode, g, q, "the element multipliers", fixed, "the fixed-node mask");
     launch_thermal_source(g, q, fixed, f_in, f_out, S(stream));
     VFEM_CATCH
 }
@@ -153,14 +211,7 @@ int vfem_thermal_source(int dim, const int64_t *nelems_host, const double *h_hos
 int vfem_thermal_band_assemble(int dim, const int64_t *nelems_host, const double *Kc0_host, const double *kappa, const uint8_t *fixed,
                                double *band, void *stream) {
     VFEM_TRY
-    const std::string w = "vfem_thermal_band_assemble";
-    const ModalGrid g = grid_args(w, dim, nelems_host, nullptr, false);
-    const ThermalMatrix K = thermal_element_matrix(w, dim, Kc0_host);
-    if (!kappa || !band) throw Error(w + ": null argument");
-    long long n, hw;
-    thermal_band_geometry(g, n, hw);
-    check_thermal_output(w, "band", g, band, band_spd_doubles(n, hw), kappa, fixed);
-    launch_thermal_band_assemble(g, K, kappa, fixed, band, S(stream));
+    band_entry("vfem_thermal_band_assemble", dim, nelems_host, Kc0_host, false, nullptr, kappa, nullptr, fixed, band, stream);
     VFEM_CATCH
 }
 
@@ -168,20 +219,39 @@ int vfem_thermal_pcg(int dim, const int64_t *nelems_host, const double *Kc0_host
                      const double *b, double *x, double tol, int max_iter, int *iterations_out_host, double *relres_out_host,
                      void *stream) {
     VFEM_TRY
-    const std::string w = "vfem_thermal_pcg";
-    hipStream_t s = S(stream);
-    const ModalGrid g = grid_args(w, dim, nelems_host, nullptr, false);
-    const ThermalMatrix K = thermal_element_matrix(w, dim, Kc0_host);
-    if (!kappa || !b || !x || !iterations_out_host || !relres_out_host) throw Error(w + ": null argument");
-    if (!(tol > 0.0) || !std::isfinite(tol) || max_iter < 1) throw Error(w + ": tol must be positive and max_iter at least 1");
-    const long long n = g.nnode;
-    if (overlaps(x, n, b, n)) throw Error(w + ": x aliases b");
-    check_thermal_output(w, "x", g, x, n, kappa, fixed);
-    DevBuf<double> dinv;
-    dinv.alloc((size_t) n);
-    launch_thermal_diagonal(g, K, kappa, fixed, 1, dinv.p, s);
-    const ThermalPreconditioner jacobi = [&](const double *r, double *z) { launch_thermal_scale(n, dinv.p, r, z, s); };
-    thermal_pcg(w, g, K, kappa, fixed, b, x, tol, max_iter, THERMAL_PCG_CHECK, jacobi, iterations_out_host, relres_out_host, s);
+    pcg_entry("vfem_thermal_pcg", dim, nelems_host, Kc0_host, false, nullptr, kappa, nullptr, fixed, b, x, tol, max_iter,
+              iterations_out_host, relres_out_host, stream);
+    VFEM_CATCH
+}
+
+int vfem_transient_apply(int dim, const int64_t *nelems_host, const double *Ka_host, const double *mb_host, const double *kappa,
+                         const double *cap, const uint8_t *fixed, int identity, int ncols, const double *X, const double *b, double *Y,
+                         void *stream) {
+    VFEM_TRY
+    apply_entry("vfem_transient_apply", dim, nelems_host, Ka_host, true, mb_host, kappa, cap, fixed, identity, ncols, X, b, Y, stream);
+    VFEM_CATCH
+}
+
+int vfem_transient_diagonal(int dim, const int64_t *nelems_host, const double *Ka_host, const double *mb_host, const double *kappa,
+                            const double *cap, const uint8_t *fixed, double *diag, void *stream) {
+    VFEM_TRY
+    diagonal_entry("vfem_transient_diagonal", dim, nelems_host, Ka_host, true, mb_host, kappa, cap, fixed, diag, stream);
+    VFEM_CATCH
+}
+
+int vfem_transient_band_assemble(int dim, const int64_t *nelems_host, const double *Ka_host, const double *mb_host, const double *kappa,
+                                 const double *cap, const uint8_t *fixed, double *band, void *stream) {
+    VFEM_TRY
+    band_entry("vfem_transient_band_assemble", dim, nelems_host, Ka_host, true, mb_host, kappa, cap, fixed, band, stream);
+    VFEM_CATCH
+}
+
+int vfem_transient_pcg(int dim, const int64_t *nelems_host, const double *Ka_host, const double *mb_host, const double *kappa,
+                       const double *cap, const uint8_t *fixed, const double *b, double *x, double tol, int max_iter,
+                       int *iterations_out_host, double *relres_out_host, void *stream) {
+    VFEM_TRY
+    pcg_entry("vfem_transient_pcg", dim, nelems_host, Ka_host, true, mb_host, kappa, cap, fixed, b, x, tol, max_iter, iterations_out_host,
+              relres_out_host, stream);
     VFEM_CATCH
 }
 

@@ -1,17 +1,21 @@
-// Device code that kernels_thermal.hip, kernels_thermal_mg.hip and kernels_transient.hip share: how a node of the
-// matrix-free scalar operator forms its couplings and finds the neighbours that take part.  Said once, so that the apply, the
-// level-0 colour sweep, the Galerkin product from level 0 and the dense fill of a one-level hierarchy sum the same terms in the same
-// order, for the conduction operator and for the two-term operator of a transient step alike.
+// Device code that kernels_thermal.hip and kernels_thermal_mg.hip share: how a node of the matrix-free scalar
+// operator forms its couplings and finds the neighbours that take part.  Said once, so that the apply, the level-0 colour sweep, the
+// Galerkin product from level 0 and the dense fill of a one-level hierarchy sum the same terms in the same order.  The one-term and
+// the two-term form of the operator (thermal.h) are two instantiations of the same text: `if constexpr` leaves the capacity lines out
+// of the one-term code, and what only the two-term form takes (mb, cap) has the empty type NoCapacity in the one-term instantiation.
 //
-// The two bodies are macros that the functions below wrap.  k_thermal_apply<3> sits at the edge of its register budget (63 VGPRs,
-// 106 SGPRs, no scratch): with the arrays handed to a function by reference the compiler schedules it differently, even though
+// The two bodies are macros that the functions below wrap.  k_thermal_apply<3> sits at the edge of its register budget (one-term:
+// 63 VGPRs, no scratch): with the arrays handed to a function by reference the compiler schedules it differently, even though
 // everything is inlined (measured: 64 VGPRs and 68 bytes of scratch per lane with the couplings in a function, 196 bytes with the
-// neighbours in one too).  Expanded in the kernel's own body the macros give the code the kernel had before the move, register for
-// register.
+// neighbours in one too; a shared inlined body behind two thin kernels, or the operator as one struct argument, cost registers or
+// lane spills in the same way: DESIGN 3.18).  Expanded in the kernel's own body the macros give the code the kernel had before the
+// move, register for register.
 #pragma once
 #include "thermal.h"
 
 #include "cell_threads.h"
+
+#include <type_traits>
 
 namespace vfem {
 
@@ -21,6 +25,20 @@ struct ThermalTraits {
     static constexpr int NB = N == 2 ? 9 : 27;          // nodes coupled to a node
     static constexpr int SELF = (NB - 1) / 2;
 };
+
+// The type of a kernel argument that only the two-term form has: T there, and an empty placeholder in the one-term instantiation
+// (never read: every use is behind `if constexpr (TWO)`).  The arguments stay flat and in one order for both forms: handing the
+// operator over as one struct costs k_thermal_apply<3> lane spills.
+struct NoCapacity {};
+template <bool TWO, class T>
+using OnlyTwoTerm = std::conditional_t<TWO, T, NoCapacity>;
+// the capacity term as a member of a multigrid source (kernels_thermal_mg.hip), where Extra is this or NoCapacity
+struct CapacityTerm {
+    ThermalCapacity mb;
+    const double *cap;
+};
+template <class Extra>
+constexpr bool has_capacity = !std::is_same<Extra, NoCapacity>::value;
 
 // kappa of the element in which the node at c is local node el; 0 outside the grid
 template <int N>
@@ -36,30 +54,20 @@ __device__ __forceinline__ double incident_kappa(const ModalGrid &g, const doubl
 }
 
 // coef[k] (double [3^N]) = the coupling of the node at c with its neighbour k (cell_threads.h: neighbour_offset) in
-// sum_e kappa[e] Kc0, before any mask: the sum over the elements that hold both of kappa[e] Kc0[el][j], elements in ascending local
-// index el, j ascending within
-#define VFEM_THERMAL_COUPLINGS(N, g, K, kappa, c, coef)                                                                                \
+// sum_e (kappa[e] K + cap[e] M(mb)), before any mask: the sum over the elements that hold both of kappa[e] K[el][j], and with TWO of
+// cap[e] mb.m[popcount(el xor j)], elements in ascending local index el, j ascending within; each pair adds its conduction term
+// first and its capacity term second.  (mb and cap are read only under TWO.)
+#define VFEM_THERMAL_COUPLINGS(N, TWO, g, K, mb, kappa, cap, c, coef)                                                                  \
     do {                                                                                                                               \
         _Pragma("unroll") for (int k_ = 0; k_ < ThermalTraits<N>::NB; ++k_) coef[k_] = 0.0;                                            \
         _Pragma("unroll") for (int el_ = 0; el_ < ThermalTraits<N>::NPE; ++el_) {                                                      \
             const double ke_ = incident_kappa<N>(g, kappa, c, el_);                                                                    \
-            _Pragma("unroll") for (int j_ = 0; j_ < ThermalTraits<N>::NPE; ++j_)                                                       \
-                coef[neighbour_of<N>(el_, j_)] = fma(ke_, K.k[el_ * ThermalTraits<N>::NPE + j_], coef[neighbour_of<N>(el_, j_)]);      \
-        }                                                                                                                              \
-    } while (0)
-
-// The two-term form of the transient operator (transient.h): the coupling in sum_e (kappa[e] Ka + cap[e] M(mb)), where
-// M(mb)[el][j] = mb.m[popcount(el xor j)] depends only on the number of axes along which the two local nodes differ.  The same loop
-// order as above; each pair adds its conduction term first and its capacity term second
-#define VFEM_TRANSIENT_COUPLINGS(N, g, K, mb, kappa, cap, c, coef)                                                                     \
-    do {                                                                                                                               \
-        _Pragma("unroll") for (int k_ = 0; k_ < ThermalTraits<N>::NB; ++k_) coef[k_] = 0.0;                                            \
-        _Pragma("unroll") for (int el_ = 0; el_ < ThermalTraits<N>::NPE; ++el_) {                                                      \
-            const double ke_ = incident_kappa<N>(g, kappa, c, el_);                                                                    \
-            const double ce_ = incident_kappa<N>(g, cap, c, el_);                                                                      \
+            [[maybe_unused]] double ce_ = 0.0;                                                                                         \
+            if constexpr (TWO) ce_ = incident_kappa<N>(g, cap, c, el_);                                                                \
             _Pragma("unroll") for (int j_ = 0; j_ < ThermalTraits<N>::NPE; ++j_) {                                                     \
                 coef[neighbour_of<N>(el_, j_)] = fma(ke_, K.k[el_ * ThermalTraits<N>::NPE + j_], coef[neighbour_of<N>(el_, j_)]);      \
-                coef[neighbour_of<N>(el_, j_)] = fma(ce_, mb.m[__builtin_popcount(el_ ^ j_)], coef[neighbour_of<N>(el_, j_)]);         \
+                if constexpr (TWO)                                                                                                     \
+                    coef[neighbour_of<N>(el_, j_)] = fma(ce_, mb.m[__builtin_popcount(el_ ^ j_)], coef[neighbour_of<N>(el_, j_)]);     \
             }                                                                                                                          \
         }                                                                                                                              \
     } while (0)
@@ -81,17 +89,10 @@ __device__ __forceinline__ double incident_kappa(const ModalGrid &g, const doubl
         }                                                                                                                              \
     } while (0)
 
-template <int N>
+template <int N, class Extra>
 __device__ __forceinline__ void thermal_couplings(const ModalGrid &g, const ThermalMatrix &K, const double *__restrict__ kappa,
-                                                  const int (&c)[N], double (&coef)[ThermalTraits<N>::NB]) {
-    VFEM_THERMAL_COUPLINGS(N, g, K, kappa, c, coef);
-}
-
-template <int N>
-__device__ __forceinline__ void transient_couplings(const ModalGrid &g, const ThermalMatrix &K, const ThermalCapacity &mb,
-                                                    const double *__restrict__ kappa, const double *__restrict__ cap, const int (&c)[N],
-                                                    double (&coef)[ThermalTraits<N>::NB]) {
-    VFEM_TRANSIENT_COUPLINGS(N, g, K, mb, kappa, cap, c, coef);
+                                                  const Extra &extra, const int (&c)[N], double (&coef)[ThermalTraits<N>::NB]) {
+    VFEM_THERMAL_COUPLINGS(N, has_capacity<Extra>, g, K, extra.mb, kappa, extra.cap, c, coef);
 }
 
 template <int N>

@@ -1,6 +1,7 @@
-// Multigrid preconditioner of the scalar conduction operator: what kernels_thermal_mg.hip offers to thermal_mg.hip.
+// Multigrid preconditioner of the scalar heat operator: what kernels_thermal_mg.hip offers to thermal_mg.hip.
 //
-// Level 0 is the grid and stays matrix-free from kappa (thermal.h).  Level l + 1 has half the elements per axis; its nodes are the
+// Level 0 is the grid and stays matrix-free from kappa, and from cap in the two-term form (thermal.h; the formulas below name the
+// conduction term alone).  Level l + 1 has half the elements per axis; its nodes are the
 // even nodes of level l, and a coarse node is fixed exactly when that fine node is.  With I_l the N-linear interpolation and F_l the
 // 0/1 diagonal of the free nodes, P_l = F_l I_l F_{l+1},
 //   A'_0 = F_0 (sum_e kappa_e Kc0) F_0,    A'_{l+1} = P_l^T A'_l P_l,    A_l = A'_l + (I - F_l).
@@ -14,14 +15,11 @@
 
 namespace vfem {
 
-// where a level's couplings come from: the stored stencil A (kappa null), or for level 0 the conductivities kappa and Kc0; with
-// cap (the hierarchy of a transient step) level 0 is the two-term operator sum_e (kappa_e K + cap_e M(mb))
+// where a level's couplings come from: the stored stencil A (fine null), or for level 0 the matrix-free operator of thermal.h, in
+// its one-term form or (the hierarchy of a transient step) its two-term form sum_e (kappa_e K + cap_e M(mb))
 struct ThermalLevelOp {
     const double *A;
-    const double *kappa;
-    const ThermalMatrix *K;         // host; read at the launch
-    const double *cap;              // null: the conduction term alone
-    const ThermalCapacity *mb;      // host; read at the launch
+    const ThermalOp *fine;          // host; read at the launch
 };
 
 // coarse mask: fixed_c[I] = fixed_f[2 I]

@@ -1,12 +1,12 @@
-// The multigrid-preconditioned PCG of the scalar conduction operator (include/vfem.h: vfem_thermal_mg_*).  A handle
-// holds the hierarchy of one grid, one set of conductivities and one mask: level 0 matrix-free from the caller's kappa, the Galerkin
-// levels stored (thermal_mg.h), the coarsest level as a dense inverse (CoarsestSolver).  The V-cycle is mg_cycle::vcycle, the colour
+// The multigrid-preconditioned PCG of the scalar heat operator (include/vfem.h: vfem_thermal_mg_*, vfem_transient_mg_create; DESIGN
+// 3.16, 3.18).  A handle holds the hierarchy of one grid, one operator (thermal.h: one-term, or the two-term form of a transient
+// step) and one mask: level 0 matrix-free from the caller's kappa and cap, the Galerkin levels stored (thermal_mg.h), the coarsest
+// level as a dense inverse (CoarsestSolver).  Nothing below level 0's launchers knows which form the operator has.  The V-cycle is mg_cycle::vcycle, the colour
 // order for_each_gs_color, the PCG loop thermal_pcg (thermal.hip) with z = V-cycle(r).  Every argument is checked before the first
 // device call.
 #include "grid_args.h"
 #include "mg_stored.h"
 #include "thermal_mg.h"
-#include "transient.h"
 
 #include <memory>
 
@@ -21,10 +21,7 @@ struct ThermalMgLevel {
 };
 
 struct vfem_thermal_mg {
-    ThermalMatrix K;
-    const double *kappa;            // the caller's, read by every level-0 kernel
-    const double *cap = nullptr;    // vfem_transient_mg_create: the caller's element capacities, and level 0 is the two-term operator
-    ThermalCapacity mb{};           //   sum_e (kappa_e K + cap_e M(mb))
+    ThermalOp fine;                 // level 0's operator: kappa (and cap) are the caller's, read by every level-0 kernel
     const uint8_t *fixed_in;        // the caller's mask (may be null); the levels use their normalised copies
     std::vector<ThermalMgLevel> lv;
     CoarsestSolver coarsest;
@@ -32,7 +29,7 @@ struct vfem_thermal_mg {
     int L() const { return (int) lv.size() - 1; }
     size_t vec(int l) const { return (size_t) lv[l].g.nnode; }
     ThermalLevelOp op(int l) const {
-        return l == 0 ? ThermalLevelOp{nullptr, kappa, &K, cap, &mb} : ThermalLevelOp{lv[l].A.p, nullptr, nullptr, nullptr, nullptr};
+        return l == 0 ? ThermalLevelOp{nullptr, &fine} : ThermalLevelOp{lv[l].A.p, nullptr};
     }
     long long bytes() const {
         size_t d = 0, m = 0;
@@ -51,8 +48,7 @@ void need_dinv0(vfem_thermal_mg *h, hipStream_t s) {
     ThermalMgLevel &v = h->lv[0];
     if (v.dinv.p) return;
     v.dinv.alloc((size_t) v.g.nnode);
-    if (h->cap) launch_transient_diagonal(v.g, h->K, h->mb, h->kappa, h->cap, v.fixed.p, 1, v.dinv.p, s);
-    else launch_thermal_diagonal(v.g, h->K, h->kappa, v.fixed.p, 1, v.dinv.p, s);
+    launch_thermal_diagonal(v.g, h->fine, v.fixed.p, 1, v.dinv.p, s);
 }
 
 // one sweep over the 2^N colours of the level's nodes, ascending (forward) or descending
@@ -67,8 +63,7 @@ void sweep(vfem_thermal_mg *h, int l, double *x, const double *b, int forward, h
 
 void level_apply(vfem_thermal_mg *h, int l, const double *x, const double *b, double *out, hipStream_t s) {
     const ThermalMgLevel &v = h->lv[l];
-    if (l == 0 && h->cap) launch_transient_apply(v.g, h->K, h->mb, h->kappa, h->cap, v.fixed.p, 1, 1, x, b, b ? 1 : 0, out, s);
-    else if (l == 0) launch_thermal_apply(v.g, h->K, h->kappa, v.fixed.p, 1, x, b, out, s);
+    if (l == 0) launch_thermal_apply(v.g, h->fine, v.fixed.p, 1, 1, x, b, 1, out, s);
     else launch_thermal_mg_apply(v.g, v.A.p, v.fixed.p, x, b, out, s);
 }
 
@@ -109,15 +104,7 @@ void create(const std::string &w, vfem_thermal_mg **out, int dim, const int64_t 
     hipStream_t s = S(stream);
     ModalGrid g = grid_args(w, dim, nelems_host, nullptr, false);
     std::unique_ptr<vfem_thermal_mg> h(new vfem_thermal_mg);
-    h->K = thermal_element_matrix(w, dim, Kc0_host);
-    if (two_term) {
-        if (!mb_host) throw Error(w + ": null argument");
-        check_finite(w, "the capacity entries are", mb_host, dim + 1);
-        for (int d = 0; d <= dim; ++d) h->mb.m[d] = mb_host[d];
-    }
-    if (!kappa || (two_term && !cap)) throw Error(w + ": null argument");
-    h->kappa = kappa;
-    h->cap = two_term ? cap : nullptr;
+    h->fine = thermal_operator_args(w, dim, Kc0_host, two_term, mb_host, kappa, cap);
     h->fixed_in = fixed;
     const int N = g.N;
     // the levels (max_coarsenings < 0: as far as the extents allow); a coarser voxel has twice the edge lengths
@@ -173,9 +160,7 @@ void create(const std::string &w, vfem_thermal_mg **out, int dim, const int64_t 
         h->coarsest.factor_dense(1, h->lv[L].fixed.p, s);
     } catch (const Error &e) {                  // a pivot that is not positive: what the PCG would report as its breakdown
         throw Error(w + ": breakdown at the coarsest level of the hierarchy " + sizes + ": " + e.what() +
-                    "; the operator is singular: " + (two_term ? "a free node whose incident elements all have zero conductivity and zero capacity"
-                                                               : "no fixed node, a free node whose incident elements all have zero conductivity") +
-                    ", or non-finite data");
+                    "; the operator is singular: " + thermal_singular_because(h->fine) + ", or non-finite data");
     }
     VFEM_HIP(hipStreamSynchronize(s));          // the factorisation's workspace is not needed again
     h->coarsest.work = DenseWork();
@@ -292,9 +277,8 @@ int vfem_thermal_mg_pcg(vfem_thermal_mg *h, const double *b, double *x, double t
     // z = V-cycle(r); the host looks after every iteration, so the count is exact: a look costs little beside a cycle
     const ThermalPreconditioner multigrid = [&](const double *r, double *z) { cycle_from_zero<ThermalOps>(h, r, z, smoothing, s); };
     const ThermalApply apply = [&](const double *v, const double *rhs, double *res) { level_apply(h, 0, v, rhs, res, s); };
-    thermal_pcg(w, g.nnode, apply, h->cap ? "a free node whose incident elements all have zero conductivity and zero capacity"
-                                          : "no fixed node, a free node whose incident elements all have zero conductivity",
-                b, x, tol, max_iter, 1, multigrid, iterations_out_host, relres_out_host, s);
+    thermal_pcg(w, g.nnode, apply, thermal_singular_because(h->fine), b, x, tol, max_iter, 1, multigrid, iterations_out_host,
+                relres_out_host, s);
     VFEM_CATCH
 }
 

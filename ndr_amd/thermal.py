@@ -60,6 +60,72 @@ def conductivityMatrix(k, h):
     return K
 
 
+def _check_solver(who, solver, preconditioner):
+    """the three refusals of every call that takes ``solver`` and ``preconditioner``"""
+    if solver not in ("direct", "pcg"):
+        raise RuntimeError("%s: solver is \"direct\" or \"pcg\" (got %r)" % (who, solver))
+    if preconditioner not in ("jacobi", "multigrid"):
+        raise RuntimeError("%s: preconditioner is \"jacobi\" or \"multigrid\" (got %r)" % (who, preconditioner))
+    if preconditioner != "jacobi" and solver != "pcg":
+        raise RuntimeError("%s: a preconditioner goes with solver=\"pcg\" (got solver %r)" % (who, solver))
+
+
+def _set_densities(sim, xPhys):
+    """the densities of a design update (None: as they are): set only if they differ, since setting them again would drop the kept
+    factor; returns whether they were set"""
+    if xPhys is None:
+        return False
+    x = _to_dev(xPhys).reshape(-1)
+    if x.shape == sim._rho.shape and torch.equal(sim._rho, x):
+        return False
+    sim.setElementDensities(x)
+    return True
+
+
+class _KeptSolvers:
+    """The band factor and the multigrid hierarchy of one operator, for ``HeatConductionSimulator`` and
+    ``ndr_amd.transient.TransientHeatSimulator``: each is built on first use, counted, and kept until ``drop()``; the hierarchy's
+    handle is destroyed there, or with the holder."""
+
+    def __init__(self):
+        self.band = self.mg = None          # mg: (handle, the arrays it reads: kept alive)
+        self.factorizations = self.builds = 0
+
+    def factor(self, assemble, n, w):
+        if self.band is None:
+            band = assemble()
+            _lib.check(_lib.load().vfem_band_spd_factor(n, w, _ptr(band), _stream()))
+            self.band = band
+            self.factorizations += 1
+        return self.band
+
+    def multigrid(self, create, operator):
+        """the handle of ``create(&handle, *args, all coarsenings, stream)``, with ``operator()`` = (args, the arrays that the handle
+        goes on reading: kept alive with it)"""
+        if self.mg is None:
+            args, alive = operator()
+            handle = ctypes.c_void_p()
+            _lib.check(create(ctypes.byref(handle), *args, -1, _stream()))
+            self.mg = (handle, alive)
+            self.builds += 1
+        return self.mg[0]
+
+    def drop_multigrid(self):
+        if getattr(self, "mg", None) is not None:
+            handle, self.mg = self.mg[0], None
+            _lib.load().vfem_thermal_mg_destroy(handle)
+
+    def drop(self):
+        self.band = None
+        self.drop_multigrid()
+
+    def __del__(self):
+        try:
+            self.drop_multigrid()
+        except Exception:
+            pass
+
+
 class HeatConductionSimulator:
     """Steady heat conduction -div(kappa k grad T) = q on a grid of ``elementsPerDimension`` voxels (2 or 3 axes) over
     ``domainBBox`` = [lower corner, upper corner].  It has what the design problem and the filters read from a simulator
@@ -96,10 +162,7 @@ class HeatConductionSimulator:
         self._mask_dev = torch.zeros(self.numNodes(), dtype=torch.uint8, device=_dev())
         self._Qn = self._qv = None
         self._Kc0 = None
-        self._band = None                   # the kept factor
-        self._factorizations = 0
-        self._mg = None                     # the kept multigrid hierarchy: (handle, kappa, mask, Kc0), the arrays it reads kept alive
-        self._mg_builds = 0
+        self._kept = _KeptSolvers()         # the band factor and the multigrid hierarchy of the present operator
         self.last_iterations = 0
         self.last_relative_residual = 0.0
 
@@ -123,20 +186,11 @@ class HeatConductionSimulator:
 
     def _changed(self):
         """the operator changed: the kept factor and the kept hierarchy no longer stand for it"""
-        self._band = None
         self._version += 1
-        self._drop_multigrid()
+        self._kept.drop()
 
     def _drop_multigrid(self):
-        if getattr(self, "_mg", None) is not None:
-            handle, self._mg = self._mg[0], None
-            _lib.load().vfem_thermal_mg_destroy(handle)
-
-    def __del__(self):
-        try:
-            self._drop_multigrid()
-        except Exception:
-            pass
+        self._kept.drop_multigrid()
 
     # ---- material ----
     def _get_conductivity(self):
@@ -300,7 +354,7 @@ class HeatConductionSimulator:
         return (n + _TILE - 1) // _TILE * ((w + _TILE - 1) // _TILE + 2) * _TILE * _TILE * 8
 
     def numDirectFactorizations(self):
-        return self._factorizations
+        return self._kept.factorizations
 
     def assembleBand_device(self):
         """the lower band of A in the tile layout of ``vfem_band_spd_factor`` (a new buffer; the factor slots are zero)"""
@@ -317,15 +371,10 @@ class HeatConductionSimulator:
         if Q.numel() != cols * self.numNodes():
             raise RuntimeError("Invalid input size")
         n, w = self._band_geometry()
-        lib = _lib.load()
-        if self._band is None:
-            band = self.assembleBand_device()
-            _lib.check(lib.vfem_band_spd_factor(n, w, _ptr(band), _stream()))
-            self._band = band
-            self._factorizations += 1
+        band = self._kept.factor(self.assembleBand_device, n, w)
         T = Q.clone()
         T.reshape(cols, n)[:, self._mask_dev.bool()] = 0.0
-        _lib.check(lib.vfem_band_spd_solve(n, w, _ptr(self._band), _ptr(T), cols, _stream()))
+        _lib.check(_lib.load().vfem_band_spd_solve(n, w, _ptr(band), _ptr(T), cols, _stream()))
         return T
 
     def solve(self, Q):
@@ -335,18 +384,13 @@ class HeatConductionSimulator:
     def _multigrid(self):
         """the hierarchy of the present operator (``vfem_thermal_mg_create``), built on first use and kept until the densities, the
         material or the mask change: the events that drop the band factor"""
-        if self._mg is None:
-            kappa = self.elementConductivities_device()[0]
-            mask, Kc0 = self._mask_dev, self._K()
-            handle = ctypes.c_void_p()
-            _lib.check(_lib.load().vfem_thermal_mg_create(ctypes.byref(handle), *self._head(), _dp(Kc0), _ptr(kappa),
-                                                          _ptr(mask) if self._mask.any() else None, -1, _stream()))
-            self._mg = (handle, kappa, mask, Kc0)
-            self._mg_builds += 1
-        return self._mg[0]
+        def operator():
+            kappa, mask, Kc0 = self.elementConductivities_device()[0], self._mask_dev, self._K()
+            return (*self._head(), _dp(Kc0), _ptr(kappa), self._fixed()), (kappa, mask, Kc0)
+        return self._kept.multigrid(_lib.load().vfem_thermal_mg_create, operator)
 
     def numMultigridBuilds(self):
-        return self._mg_builds
+        return self._kept.builds
 
     def multigridLevels(self):
         """the elements per axis of every level of the hierarchy (built if need be)"""
@@ -367,8 +411,7 @@ class HeatConductionSimulator:
         (``preconditioner="multigrid"``) one V-cycle of ``smoothing`` sweeps before and after the coarse correction;
         ``last_iterations`` and ``last_relative_residual`` are those of this solve.  Raises when ``maxIter`` is reached or the
         operator is singular."""
-        if preconditioner not in ("jacobi", "multigrid"):
-            raise RuntimeError("pcg_device: preconditioner is \"jacobi\" or \"multigrid\" (got %r)" % (preconditioner,))
+        _check_solver("pcg_device", "pcg", preconditioner)
         self._need_sink("pcg_device")
         Q = _to_dev(Q, (self.numNodes(),))
         x = torch.zeros_like(Q) if x0 is None else _to_dev(x0, (self.numNodes(),)).clone()
@@ -430,12 +473,7 @@ class ThermalComplianceObjective:
     def __init__(self, heat, solver="direct", skipSolve=False, preconditioner="jacobi"):
         if not isinstance(heat, HeatConductionSimulator):
             raise TypeError("ThermalComplianceObjective takes a HeatConductionSimulator (got %r)" % (type(heat).__name__,))
-        if solver not in ("direct", "pcg"):
-            raise RuntimeError("ThermalComplianceObjective: solver is \"direct\" or \"pcg\" (got %r)" % (solver,))
-        if preconditioner not in ("jacobi", "multigrid"):
-            raise RuntimeError("ThermalComplianceObjective: preconditioner is \"jacobi\" or \"multigrid\" (got %r)" % (preconditioner,))
-        if preconditioner != "jacobi" and solver != "pcg":
-            raise RuntimeError("ThermalComplianceObjective: a preconditioner goes with solver=\"pcg\" (got solver %r)" % (solver,))
+        _check_solver("ThermalComplianceObjective", solver, preconditioner)
         self._sim, self.solver, self.preconditioner = heat, solver, preconditioner
         self.tol, self.maxIter, self.smoothing = 1e-8, 2000, 1
         self.iterations = 0
@@ -454,10 +492,7 @@ class ThermalComplianceObjective:
 
     def updateCache(self, xPhys):
         sim = self._sim
-        if xPhys is not None:
-            x = _to_dev(xPhys).reshape(-1)
-            if not (x.shape == sim._rho.shape and torch.equal(sim._rho, x)):         # (setting them again would drop the band factor)
-                sim.setElementDensities(x)
+        _set_densities(sim, xPhys)
         Q = sim.buildLoadVector_device()
         T = self._solve(Q, self._u)
         J = float(torch.dot(Q, T))
@@ -515,11 +550,7 @@ class PNormTemperatureObjective:
 
     def updateCache(self, xPhys):
         sim, so = self._sim, self.solved
-        if xPhys is not None:
-            x = _to_dev(xPhys).reshape(-1)
-            if so._u is None or not (x.shape == sim._rho.shape and torch.equal(sim._rho, x)):
-                so.updateCache(x)
-        elif so._u is None:
+        if _set_densities(sim, xPhys) or so._u is None:
             so.updateCache(None)
         self._measure()
 

@@ -36,7 +36,7 @@ import torch
 from . import _lib
 from ._grid import ObjectiveFunction, _dp
 from .pyVoxelFEM import _dev, _ptr, _stream, _to_dev, _to_np
-from .thermal import HeatConductionSimulator
+from .thermal import HeatConductionSimulator, _check_solver, _KeptSolvers, _set_densities
 
 __all__ = ["TransientHeatSimulator", "TransientComplianceObjective", "TransientPNormTemperatureObjective", "TransientComplianceFunction",
            "TransientPNormTemperatureFunction", "transientCompliance", "transientPNormTemperature", "capacityEntries"]
@@ -77,10 +77,8 @@ class TransientHeatSimulator:
             raise TypeError("TransientHeatSimulator takes a HeatConductionSimulator (got %r)" % (type(heat).__name__,))
         self.heat = heat
         self._capacity, self._q, self._c_min, self._lumping = 1.0, 1.0, 1e-3, 0.0
-        self._kept = None                   # what the kept factor or hierarchy stands for: (heat's version, dt, theta)
-        self._band = None
-        self._mg = None                     # (handle, kappa, cap, mask, Ka, mb): the arrays the handle reads, kept alive
-        self._factorizations = self._mg_builds = 0
+        self._kept = _KeptSolvers()         # the band factor and the multigrid hierarchy of A,
+        self._kept_at = None                #   and what they stand for: (heat's version, dt, theta)
         self._march = None                  # the scheme and the solver of the last march, for the adjoint
         self.last_iterations = []
         self.capacity, self.capacityExponent, self.c_min, self.lumping = capacity, capacityExponent, c_min, lumping
@@ -104,22 +102,14 @@ class TransientHeatSimulator:
     del _param
 
     def _drop(self):
-        self._band = self._kept = None
-        if getattr(self, "_mg", None) is not None:
-            handle, self._mg = self._mg[0], None
-            _lib.load().vfem_thermal_mg_destroy(handle)
-
-    def __del__(self):
-        try:
-            self._drop()
-        except Exception:
-            pass
+        self._kept_at = None
+        self._kept.drop()
 
     def numDirectFactorizations(self):
-        return self._factorizations
+        return self._kept.factorizations
 
     def numMultigridBuilds(self):
-        return self._mg_builds
+        return self._kept.builds
 
     def numNodes(self):
         return self.heat.numNodes()
@@ -193,31 +183,22 @@ class TransientHeatSimulator:
     # ---- the kept factor or hierarchy ----
     def _stand_at(self, dt, theta):
         key = (self.heat._version, dt, theta)
-        if self._kept != key:
+        if self._kept_at != key:
             self._drop()
-            self._kept = key
+            self._kept_at = key
 
     def _factor(self, dt, theta):
         self._stand_at(dt, theta)
-        if self._band is None:
-            band = self.assembleBand_device(dt, theta)
-            n, w = self.heat._band_geometry()
-            _lib.check(_lib.load().vfem_band_spd_factor(n, w, _ptr(band), _stream()))
-            self._band = band
-            self._factorizations += 1
-        return self._band
+        return self._kept.factor(lambda: self.assembleBand_device(dt, theta), *self.heat._band_geometry())
 
     def _multigrid(self, dt, theta):
         self._stand_at(dt, theta)
-        if self._mg is None:
+
+        def operator():
             Ka, mb, kappa, cap = self._operator(theta, 1.0 / dt)
-            mask = self.heat._mask_dev
-            handle = ctypes.c_void_p()
-            _lib.check(_lib.load().vfem_transient_mg_create(ctypes.byref(handle), *self.heat._head(), _dp(Ka), _dp(mb), _ptr(kappa),
-                                                            _ptr(cap), self.heat._fixed(), -1, _stream()))
-            self._mg = (handle, kappa, cap, mask, Ka, mb)
-            self._mg_builds += 1
-        return self._mg[0]
+            return ((*self.heat._head(), _dp(Ka), _dp(mb), _ptr(kappa), _ptr(cap), self.heat._fixed()),
+                    (kappa, cap, self.heat._mask_dev, Ka, mb))
+        return self._kept.multigrid(_lib.load().vfem_transient_mg_create, operator)
 
     def _solve(self, m, rhs, x0):
         """A^-1 rhs (rhs is zero at the fixed nodes) through the solver of the march ``m``; returns (x, iterations)"""
@@ -250,13 +231,8 @@ class TransientHeatSimulator:
         if steps < 1:
             raise RuntimeError("march_device: steps must be at least 1 (got %r)" % (steps,))
         dt, theta = _scheme("march_device", dt, theta)
-        if solver not in ("direct", "pcg"):
-            raise RuntimeError("march_device: solver is \"direct\" or \"pcg\" (got %r)" % (solver,))
-        if preconditioner not in ("jacobi", "multigrid"):
-            raise RuntimeError("march_device: preconditioner is \"jacobi\" or \"multigrid\" (got %r)" % (preconditioner,))
-        if preconditioner != "jacobi" and solver != "pcg":
-            raise RuntimeError("march_device: a preconditioner goes with solver=\"pcg\" (got solver %r)" % (solver,))
-        s = np.ones(steps + 1) if sourceScale is None else np.asarray(sourceScale, dtype=np.float64).reshape(-1)
+        _check_solver("march_device", solver, preconditioner)
+        s =np.ones(steps + 1) if sourceScale is None else np.asarray(sourceScale, dtype=np.float64).reshape(-1)
         if s.size != steps + 1 or not np.isfinite(s).all():
             raise RuntimeError("march_device: sourceScale holds steps + 1 = %d finite values" % (steps + 1))
         n = self.numNodes()
@@ -347,12 +323,7 @@ class _TransientObjective:
         if self.steps < 1:
             raise RuntimeError("%s: steps must be at least 1 (got %r)" % (name, steps))
         self.dt, self.theta = _scheme(name, dt, theta)
-        if solver not in ("direct", "pcg"):
-            raise RuntimeError("%s: solver is \"direct\" or \"pcg\" (got %r)" % (name, solver))
-        if preconditioner not in ("jacobi", "multigrid"):
-            raise RuntimeError("%s: preconditioner is \"jacobi\" or \"multigrid\" (got %r)" % (name, preconditioner))
-        if preconditioner != "jacobi" and solver != "pcg":
-            raise RuntimeError("%s: a preconditioner goes with solver=\"pcg\" (got solver %r)" % (name, solver))
+        _check_solver(name, solver, preconditioner)
         self.solver, self.preconditioner = solver, preconditioner
         self.tol, self.maxIter, self.smoothing = 1e-8, 2000, 1
         self.T0 = None if T0 is None else _to_dev(T0, (self._sim.numNodes(),)).clone()
@@ -366,11 +337,8 @@ class _TransientObjective:
 
     def updateCache(self, xPhys):
         sim = self._sim
-        if xPhys is not None:
-            x = _to_dev(xPhys).reshape(-1)
-            if not (x.shape == sim._rho.shape and torch.equal(sim._rho, x)):         # (setting them again would drop the factor)
-                sim.setElementDensities(x)
-        T = self.transient.march_device(self.steps, self.dt, self.theta, self.T0, self.s, self.solver, self.preconditioner, self.tol,
+        _set_densities(sim, xPhys)
+        T =self.transient.march_device(self.steps, self.dt, self.theta, self.T0, self.s, self.solver, self.preconditioner, self.tol,
                                         self.maxIter, self.smoothing)
         self.iterations = list(self.transient.last_iterations)
         self._marched = self.transient.lastMarch()
