@@ -99,6 +99,41 @@ def gradient(op, lam, Phi):
     return g
 
 
+def kernel_gradient(ne, h, K0, dE, dm, Phi, cK, cM):
+    """what vfem_modal_gradient computes, element by element in np.longdouble: (g [elements], S [elements]) with
+
+        g_e = dE_e sum_i cK_i phi_ie^T K0 phi_ie + dm_e sum_i cM_i phi_ie^T M0 phi_ie,   M0 = mass_element(h),
+
+    and S_e the same sum with every product replaced by its absolute value (what a rounding error of the sum is measured
+    against).  Phi [modes, ndof]; K0 any [ke, ke] matrix (only its symmetric part enters g, every entry enters S)."""
+    ld = np.longdouble
+    dofs = sc.element_dofs(ne)
+    K0, M0 = np.asarray(K0, dtype=ld), mass_element(np.asarray(h, dtype=ld))
+    dE, dm = np.asarray(dE, dtype=ld).reshape(-1), np.asarray(dm, dtype=ld).reshape(-1)
+    Phi = np.asarray(Phi, dtype=ld).reshape(len(cK), -1)
+    cK, cM = np.asarray(cK, dtype=ld), np.asarray(cM, dtype=ld)
+    aK0, aM0, acK, acM = np.abs(K0), np.abs(M0), np.abs(cK), np.abs(cM)
+    g, S = np.zeros(len(dofs), dtype=ld), np.zeros(len(dofs), dtype=ld)
+    for e in range(len(dofs)):
+        p = Phi[:, dofs[e]]                                   # [modes, ke]: the modes' values on this element
+        a = np.abs(p)
+        qK, qM = np.sum(p @ K0 * p, axis=1), np.sum(p @ M0 * p, axis=1)
+        aK, aM = np.sum(a @ aK0 * a, axis=1), np.sum(a @ aM0 * a, axis=1)
+        g[e] = dE[e] * np.sum(cK * qK) + dm[e] * np.sum(cM * qM)
+        S[e] = abs(dE[e]) * np.sum(acK * aK) + abs(dm[e]) * np.sum(acM * aM)
+    return g, S
+
+
+def kernel_gradient_chain(N, nmodes):
+    """L, the roundings one product of g_e can pass through in k_modal_gradient (kernels_modal.hip), so that
+    |computed - g_e| <= L 2^-53 / (1 - L 2^-53) S_e <= 2 L 2^-53 S_e.  Per mode, with ke = N 2^N: ke^2 multiply-adds of the rows of
+    K0 and ke that add the rows to phi^T K0 phi; N ke additions of the mass term's axis passes (2 t + t': the doubling is exact)
+    and ke multiply-adds of phi^T M0 phi; at most 2 N for prod h_d / 6, one for its product with the mass term, and one
+    multiply-add into each of the two sums over the modes.  Then dE_e sK + dm_e sM: a product and a multiply-add."""
+    ke = N * 2 ** N
+    return nmodes * (ke * ke + ke + (N * ke + ke) + 2 * N + 3) + 2
+
+
 # ---- LOBPCG with the basis handling of ndr_amd.modal ----
 
 RANK_TOL = 1e-3         # see ndr_amd.modal._RANK_TOL; 1e-7 let the residuals jump back from 1e-11 to 1e-8, 1e-2 stalled 8 x 8 x 6 at 5e-7

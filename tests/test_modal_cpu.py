@@ -9,7 +9,16 @@ face clamped, four modes.  Measured here:
   and X^T M X within 2.3e-15 / 3.8e-15 of the identity; at tol 1e-12 it takes 19 / 18 iterations, and its residuals then hover
   between 1e-12 and 1e-11 on 16 x 12 (the rounding floor 2^-53 lambda_max / lambda_1 is 3.7e-12 there);
   the central difference of J (step 1e-5, dense solves) misses the gradient by 6.57e-8 (16 x 12) and 9.19e-9 (8 x 8 x 6);
-  the gradient of J has 71 positive and 121 negative entries on 16 x 12, 147 and 237 on 8 x 8 x 6.
+  the gradient of J has 71 positive and 121 negative entries on 16 x 12, 147 and 237 on 8 x 8 x 6;
+  at the other block sizes (modes + guard columns; tests/test_gpu_modal_blocks.py takes its bounds from these) the LOBPCG takes, with
+  eigenvalue errors relative to the largest one asked for and X^T M X - I,
+      1 + 0:  7 iterations, 5.72e-13, 6.7e-16 (16 x 12)   and 17, 3.23e-13, 1.1e-16 (8 x 8 x 6)
+      1 + 2:  6, 5.77e-13, 4.4e-16                        and  8, 3.18e-13, 1.1e-15
+      2 + 2:  9, 7.10e-14, 2.2e-16                        and  8, 2.42e-13, 1.4e-15
+      8 + 0: 22, 1.07e-14, 2.6e-15                        and 18, 2.20e-14, 1.1e-15
+  and on buckling_cpu's column2 with one mode and two guard columns 9 iterations, 9.13e-14 of |nu_1|, phi^T K phi - 1 7.9e-14;
+  modal_cpu.kernel_gradient (np.longdouble) differs from modal_cpu.gradient (float64) by 1.8e-16 / 1.7e-16 of the sum of the
+  absolute values of its products on the two fixtures.
 """
 import numpy as np
 import pytest
@@ -18,6 +27,7 @@ import modal_cpu as mc
 import stress_cpu as sc
 
 NAMES = ["16x12", "8x8x6"]
+BLOCKS = [(1, 0), (1, 2), (2, 2), (8, 0)]          # (modes, guard columns): the block sizes m = 1, 3, 4, 8
 
 
 @pytest.mark.parametrize("h", [(0.5, 0.3), (0.5, 0.3, 0.7)])
@@ -70,6 +80,74 @@ def test_lobpcg_matches_the_dense_solver(name):
     # a warm start from the converged block finishes at once
     again = mc.lobpcg(op["K"], op["M"], mc.NUM_MODES, 1e-9, np.hstack([X, mc.start_block(op, 2, seed=8)]))
     assert again[2] <= 2
+
+
+@pytest.mark.parametrize("modes,guard", BLOCKS)
+@pytest.mark.parametrize("name", NAMES)
+def test_lobpcg_at_the_other_block_sizes(name, modes, guard):
+    """prints the figures the bounds of tests/test_gpu_modal_blocks.py are ten times of (its docstring quotes them)"""
+    op = mc.reference(name)["op"]
+    want = mc.reference(name)["spectrum"][:modes]
+    lam, X, its, res = mc.lobpcg(op["K"], op["M"], modes, 1e-9, mc.start_block(op, modes + guard), guard=guard)
+    err = np.abs(lam - want).max() / want.max()
+    orth = np.abs(X.T @ (op["M"] @ X) - np.eye(modes)).max()
+    print("lobpcg %s, %d modes + %d guard: %d iterations, eigenvalues %.2e, X^T M X - I %.2e, residuals %.2e" % (name, modes, guard, its, err, orth, res.max()))
+    assert res.max() <= 1e-9 and err < 1e-11 and orth < 1e-12 and its <= 30
+    block = np.hstack([X, mc.start_block(op, guard, seed=8)]) if guard else X
+    assert mc.lobpcg(op["K"], op["M"], modes, 1e-9, block, guard=guard)[2] <= 2
+
+
+def test_buckling_lobpcg_with_one_mode():
+    """the shared driver with the other pair of operators at m = 3: the figures behind test_gpu_modal_blocks' buckling bound"""
+    import buckling_cpu as bc
+    ref = bc.reference("column2")
+    op = ref["op"]
+    nu, Phi, its, res = bc.lobpcg_modes(op, 1, 1e-9, bc.start_block(op, 3))
+    err = abs(nu[0] - ref["nu"][0]) / abs(ref["nu"][0])
+    p = Phi[op["free"]]
+    orth = abs(float((p.T @ (op["K"] @ p))[0, 0]) - 1.0)
+    print("buckling lobpcg column2, 1 mode + 2 guard: %d iterations, nu %.2e, phi^T K phi - 1 %.2e, residual %.2e" % (its, err, orth, res.max()))
+    assert res.max() <= 1e-9 and err < 1e-11 and orth < 1e-12 and its <= 30
+
+
+def _gradient_bound(ne, nmodes):
+    """the bound the device kernel is held to (tests/test_gpu_modal_blocks.py); float64 numpy sums have no longer chains"""
+    return 2.0 * mc.kernel_gradient_chain(len(ne), nmodes) * 2.0 ** -53
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_kernel_gradient_is_the_gradient_on_the_fixtures(name):
+    ref = mc.reference(name)
+    op, lam = ref["op"], ref["lam"]
+    ne, h = mc.CASES[name][0], mc.CASES[name][1]
+    g, S = mc.kernel_gradient(ne, h, op["K0"], op["dE"], op["dm"], ref["Phi"].T, -lam ** -2.0, 1.0 / lam)
+    ratio = (np.abs(g - ref["gradient"]) / S).max().astype(np.float64)
+    print("kernel_gradient against gradient, %s: %.2e of S (bound %.2e)" % (name, ratio, _gradient_bound(ne, len(lam))))
+    assert g.dtype == np.longdouble and (S > 0).all() and (np.abs(g) <= S).all()
+    assert ratio < _gradient_bound(ne, len(lam))
+
+
+def test_kernel_gradient_is_the_derivative_of_the_assembled_matrices():
+    """on 3 x 2, a random block, coefficients of both signs and a random (unsymmetric) element matrix:
+    g_e = sum_i cK_i phi_i^T dK/drho_e phi_i + cM_i phi_i^T dM/drho_e phi_i with the two derivatives assembled by scipy"""
+    ne, h = (3, 2), (0.5, 0.3)
+    rng = np.random.default_rng(31)
+    nel, nd = 6, sc.num_nodes(ne) * 2
+    K0 = rng.standard_normal((8, 8))
+    dE, dm, Phi = rng.standard_normal(nel), rng.standard_normal(nel), rng.standard_normal((3, nd))
+    cK, cM = np.array([0.7, -1.3, 0.4]), np.array([-0.6, 0.9, 1.1])
+    g, S = mc.kernel_gradient(ne, h, K0, dE, dm, Phi, cK, cM)
+    free = np.zeros(nd, dtype=bool)
+    for e in range(nel):
+        one = np.zeros(nel)
+        one[e] = 1.0
+        dK = sc.assemble(ne, K0, dE * one, free).toarray()
+        dM = mc.assemble_mass(ne, h, dm * one).toarray()
+        want = sum(cK[i] * Phi[i] @ dK @ Phi[i] + cM[i] * Phi[i] @ dM @ Phi[i] for i in range(3))
+        assert abs(float(g[e]) - want) < _gradient_bound(ne, 3) * float(S[e])
+    # the symmetric part of K0 alone enters the value, every entry the sum of absolute values
+    gs, Ss = mc.kernel_gradient(ne, h, 0.5 * (K0 + K0.T), dE, dm, Phi, cK, cM)
+    assert np.abs(gs - g).max() < 1e-15 * S.max() and (Ss <= S * (1 + 1e-15)).all() and (Ss < S).any()
 
 
 @pytest.mark.parametrize("name", NAMES)
